@@ -23,11 +23,27 @@ launcher (no WORLD_SIZE in the environment) starts the N ranks itself, before
 any GPU call, and exits with their status; under a launcher WORLD_SIZE must
 equal --gpus.
 
-After the timed region (rank 0, one GPU): the CPU baseline (the C oracle on
-this host's cores), the "Pd match vs CPU" check at the config's informative
-grid point (where Pd is neither 0 nor 1: exact counts on shared trial ids plus
-a 3-sigma binomial test against a large independent GPU sample), and the C0
-demo preset run in full on both sides.
+A plain run does only what the headline figure needs: setup, warmup, the timed
+steps, the outputs (`--dump-outputs DIR`) and the result line.  `--full` adds the
+rest: the box record (rocm-smi before the first GPU call, clocks sampled under
+load), the same steps again with early decision, and after the timed region
+(rank 0, one GPU) the CPU baseline (the C oracle on this host's cores), the "Pd
+match vs CPU" check at the config's informative grid point (where Pd is neither
+0 nor 1: exact counts on shared trial ids plus a 3-sigma binomial test against a
+large independent GPU sample), the C0 demo preset run in full on both sides, and
+the headline workload at the reference's own call shape.
+
+`--dump-outputs DIR` writes what the timed steps computed, as float64 .npy files
+(rank 0): counts.npy, the success counts [p, (H1, H2)] the detector launches
+accumulated over the timed steps (summed over the ranks); counts_last_step.npy,
+the last timed step's share of them; streams_sample.npy, a fixed seeded sample of
+the received words the generator launches of the last step wrote (none when the
+fused kernel keeps the streams on chip); sums_sample.npy, the fp64 log-likelihood
+sums (log P̂1, log T_ref) of a fixed seeded sample of the last step's sequences,
+from one more detector launch over the same streams after the timed region (the
+timed launches return counts only; the fused kernel: (logp1, logp1_ref, logp2,
+logp2_ref) of the last step's first trials).  Inputs are keyed by --seed and the
+global trial ids, so two runs with the same arguments give the same files.
 
 Prints ONE JSON line on rank 0.
 """
@@ -75,8 +91,15 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="nccl (= RCCL, one GPU per rank); gloo only to rehearse the multi-rank path")
-    ap.add_argument("--steps", type=int, default=6)
+    ap.add_argument("--steps", type=int, default=6, help="timed steps")
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="also everything beside the headline figure: the box record, the early-decision "
+                         "rerun (--early-decision), the CPU baseline, Pd match, C0 demo and reference-call "
+                         "legs (--cpu-baseline)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the timed steps' outputs to DIR/<name>.npy (float64): counts, "
+                         "counts_last_step, streams_sample, sums_sample")
     ap.add_argument("--config", default="m6", choices=["m6", "m2", "r23_m4", "c4"],
                     help="m6 (headline, BASELINE configs[2]), m2 (configs[1]), r23_m4 (configs[3]), c4 "
                          "(configs[4]: the m6 pair over the N-sweep x p-grid, a fixed total of trials sharded "
@@ -116,14 +139,14 @@ def parse():
                          "automaton, no streams in HBM); -1: auto = where the library prefers it "
                          "(cvd_model_info.mc_fused: small tables, e.g. m2)")
     ap.add_argument("--cpu-baseline", type=int, default=1,
-                    help="time the C oracle port on this host (rank 0, one GPU), check Pd against it at "
+                    help="with --full: time the C oracle port on this host (rank 0, one GPU), check Pd against it at "
                          "the config's informative point, and run the C0 demo preset on both sides")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU work per timed CPU sample")
     ap.add_argument("--cpu-threads", type=int, default=None,
                     help="C oracle threads (default: the host CPUs this process may run on, capped by "
                          "OMP_NUM_THREADS when set -- the GPU box's CPU share)")
     ap.add_argument("--early-decision", type=int, default=1,
-                    help="also time the same steps with early decision (counts only; a trial stops once "
+                    help="with --full: also time the same steps with early decision (counts only; a trial stops once "
                          "its decision is certain) and check its counts equal the full run's -- reported "
                          "beside the headline, which always runs every step of every trial")
     ap.add_argument("--pmc-traffic", default=None,
@@ -272,8 +295,8 @@ def main():
     # (before any GPU call: rocm-smi in child processes; not under a profiler, whose preloaded
     # library would initialise the GPU in those children before their interpreter's exec)
     profiled = any(k.startswith("ROCPROF") for k in os.environ) or "rocprof" in os.environ.get("LD_PRELOAD", "")
-    box = box_identity() if (int(os.environ.get("RANK", "0")) == 0 and os.environ.get("CVD_BENCH_SMI", "1") != "0"
-                             and not profiled) else None
+    box = box_identity() if (a.full and int(os.environ.get("RANK", "0")) == 0
+                             and os.environ.get("CVD_BENCH_SMI", "1") != "0" and not profiled) else None
     import numpy as np
     import torch
     from __graft_entry__ import load_package
@@ -417,9 +440,12 @@ def main():
         if ev is not None:
             ev[1].record(st)
 
-    def run(steps, base, ev=None):
+    before_last = [None]    # --dump-outputs: the counts as the last timed step found them
+
+    def run(steps, base, ev=None, snap=False):
         """steps from step `base`; ev: {"gen": per unit, "det": [step][group], "end": per step
-        (main stream, after the step's detector launches), "t0": start}"""
+        (main stream, after the step's detector launches), "t0": start}; snap: copy the counts
+        on the main stream before the last step's detector launches (--dump-outputs)"""
         if steps <= 0:
             return
         if ev is not None:
@@ -434,6 +460,8 @@ def main():
                     ready.record(main)
                     for q in queues[1:]:
                         q.wait_event(ready)
+                if snap and s == steps - 1:
+                    before_last[0] = counts.clone()
                 # (nq > 1: the largest group goes last on the main queue, the others first on
                 # their own queues, so their last rounds overlap the large launch)
                 order = sorted(range(len(groups)), key=lambda g: len(groups[g])) if nq > 1 else range(len(groups))
@@ -455,6 +483,8 @@ def main():
         for x in range(nu):
             s, j, u = flat[x]
             main.wait_event(ready[x])
+            if snap and s == steps - 1 and j == 0:
+                before_last[0] = counts.clone()
             detect([u], [bufs[x % 2]], main, ev["det"][s][j] if ev else None)
             done[x].record(main)
             if ev is not None and j == per_step - 1:
@@ -492,7 +522,7 @@ def main():
     ev = make_events(a.steps)
     sampler = ClockSampler().start() if box is not None else None
     t0 = time.perf_counter()
-    run(a.steps, 0, ev)
+    run(a.steps, 0, ev, snap=bool(a.dump_outputs))
     shard = counts.clone() if dist else None   # this rank's own counts (reduce_record checks the reduce)
     if dist:
         dist.all_reduce(counts)                # the one collective: success counts over RCCL
@@ -512,6 +542,29 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         return [float(v) for v in t.tolist()] if isinstance(x, list) else float(t[0])
 
+    if a.dump_outputs:
+        last = (shard if dist else counts) - before_last[0]
+        if dist:
+            dist.all_reduce(last)
+        if rank == 0:
+            arrays = {"counts": counts.cpu().numpy(), "counts_last_step": last.cpu().numpy()}
+            if nbuf:
+                # the last unit's buffer; only the words the generator writes (not the padding)
+                buf = bufs[(a.steps * per_step - 1) % 2 if a.overlap else per_step - 1]
+                arrays["streams_sample"] = sample_words(buf, -(-N // (32 // n)), 2 * B, a.seed)
+            # the timed launches return counts only (and the m6 sweep's Pd is 0): one more detector
+            # launch over the last unit's streams, with the per-sequence fp64 sums
+            i_last, tb_last = units(a.steps - 1)[-1]
+            if nbuf and not parity:
+                sums = torch.full((2 * B, 2), float("nan"), dtype=torch.float64, device=det.device)
+                det.detect(models[p_grid[i_last]], buf, N, 2 * B, B, sums=sums, stream=main)
+                rows = np.random.default_rng(a.seed).integers(0, 2 * B, size=min(2 * B, DUMP_SAMPLE_ROWS))
+                arrays["sums_sample"] = sums[torch.from_numpy(rows).to(det.device)].cpu().numpy()
+            elif a.fused:
+                arrays["sums_sample"] = det.run_trials(
+                    models[p_grid[i_last]], cc["gen1"], cc["gen2"], N, p_grid[i_last], a.seed, tb_last,
+                    tb_last + min(B, DUMP_SAMPLE_ROWS // 2), return_sums=True, fused=True)["sums"]
+            dump_outputs(a.dump_outputs, arrays)
     st_ms = step_times(ev, a.steps)
     if dist:
         elapsed = max_over_ranks(elapsed)
@@ -541,7 +594,7 @@ def main():
 
     # the same steps (same trial ids) with early decision: counts must be identical
     early_out = None
-    if a.early_decision and not parity:
+    if a.full and a.early_decision and not parity:
         full_counts = counts.clone()
         counts.zero_()
         early[0] = True
@@ -762,7 +815,7 @@ def main():
     out["box"] = box
     bufs.clear()                               # the stream buffers (up to 2 x 131 GB) before the legs below
     torch.cuda.empty_cache()
-    if a.cpu_baseline and world == 1 and not parity:
+    if a.full and a.cpu_baseline and world == 1 and not parity:
         host = host_info(a.cpu_threads)
         out["cpu_baseline"], _ = cpu_baseline(cc, k, n, m, N, a.seed, a.learn_len, a.cpu_seconds, host)
         out["pd_match_vs_cpu"] = pd_match(pkg, det, cc, a.config, k, n, m, a.seed, a.cpu_seconds, host)
@@ -922,12 +975,41 @@ def run_c4(a, pkg, world, rank, local, dist):
         "distributed": dist_rec,
         "diagnostic": {"model_setup_s": t_setup, "elapsed_s": elapsed},
     }
-    if a.cpu_baseline and world == 1:
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, {"counts": c})
+    if a.full and a.cpu_baseline and world == 1:
         host = host_info(a.cpu_threads)
         out["cpu_baseline"], _ = cpu_baseline(cc, k, n, m, 100_000, a.seed, a.learn_len, a.cpu_seconds, host)
     print(json.dumps(out, default=_json_default), flush=True)
     if dist:
         dist.destroy_process_group()
+
+
+DUMP_SAMPLE_WORDS = 1 << 20
+DUMP_SAMPLE_ROWS = 1 << 20
+
+
+def sample_words(buf, words, nseq, seed, count=DUMP_SAMPLE_WORDS):
+    """`count` received words of a stream buffer ([W/4, pitch, 4] int32, include/cvd.h layout) at
+    (word, sequence) positions drawn once from `seed`, word < `words`, sequence < `nseq`; as
+    float64 (exact for the unsigned 32-bit words)."""
+    import numpy as np
+    import torch
+    rng = np.random.default_rng(seed)
+    count = min(count, words * nseq)
+    w = rng.integers(0, words, size=count)
+    q = rng.integers(0, nseq, size=count)
+    flat = ((w // 4) * buf.shape[1] + q) * 4 + w % 4
+    got = buf.view(-1)[torch.from_numpy(flat).to(buf.device)].cpu().numpy()
+    return got.astype(np.int64) & 0xFFFFFFFF
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: each array as <path>/<name>.npy in float64 (the counts are far below 2^53)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, arr in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.asarray(arr, dtype=np.float64))
 
 
 def reduce_record(dist, shard, reduced, world, rank, sharding):

@@ -8,7 +8,7 @@ export TMPDIR=/tmp
 if [ "${2:-}" = "tests" ]; then
   bash profiles/run_gpu_tests.sh "$OUT" || exit 1
 fi
-timeout -k 10 900 python3 bench.py --gpus 1 --steps 20 --warmup 5 > "$OUT/bench_driver_cmd.json" 2> "$OUT/bench_driver_cmd.err" \
+timeout -k 10 900 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > "$OUT/bench_driver_cmd.json" 2> "$OUT/bench_driver_cmd.err" \
   || { tail "$OUT/bench_driver_cmd.err"; exit 1; }
 python3 - "$OUT/bench_driver_cmd.json" <<'PY'
 import json, sys

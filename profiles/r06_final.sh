@@ -10,7 +10,7 @@ mkdir -p "$OUT"
 export TMPDIR=/tmp
 ROOT=$(pwd)
 bash profiles/run_gpu_tests.sh "$OUT" || exit 1
-timeout -k 10 900 python3 bench.py --gpus 1 --steps 20 --warmup 5 > "$OUT/bench_driver_cmd.json" 2> "$OUT/bench_driver_cmd.err" \
+timeout -k 10 900 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > "$OUT/bench_driver_cmd.json" 2> "$OUT/bench_driver_cmd.err" \
   || { tail "$OUT/bench_driver_cmd.err"; exit 1; }
 python3 -c "import json;d=json.loads(open('$OUT/bench_driver_cmd.json').read().strip().splitlines()[-1]);print('driver cmd',round(d['value']),round(d['roofline']['avg_launch_ms'],2),d['cpu_baseline']['value'],d['reference_call']['second_call_s'])"
 timeout -k 10 900 rocprofv3 --kernel-trace --stats -T --output-format csv -d "$ROOT/$OUT/trace" -o run \

@@ -49,6 +49,33 @@ def test_sweep_all_value_is_trials_over_time():
         b.sweep_value([], 6, 1, 1)
 
 
+def test_full_is_off_by_default_and_outputs_are_float64(monkeypatch, tmp_path):
+    """A plain command line asks for none of the --full legs; --dump-outputs files are float64,
+    and the stream sample reads seeded (word, sequence) positions of the [W/4, pitch, 4] layout,
+    never the padding words."""
+    import numpy as np
+    import torch
+    b = _bench()
+    monkeypatch.setattr("sys.argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = b.parse()
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+    monkeypatch.setattr("sys.argv", ["bench.py", "--full", "--dump-outputs", str(tmp_path)])
+    a = b.parse()
+    assert a.full is True and a.dump_outputs == str(tmp_path)
+    b.dump_outputs(str(tmp_path / "d"), {"counts": np.array([[3, 1 << 40]], dtype=np.int64)})
+    c = np.load(tmp_path / "d" / "counts.npy")
+    assert c.dtype == np.float64 and c.tolist() == [[3.0, float(1 << 40)]]
+    W, pitch, words = 8, 5, 6                       # words 6 and 7 of a sequence are padding
+    w, q = np.meshgrid(np.arange(W), np.arange(pitch), indexing="ij")
+    val = np.where(w < words, w * 1000 + q, -1)     # word w of sequence q; padding is -1
+    buf = torch.from_numpy(val.reshape(W // 4, 4, pitch).transpose(0, 2, 1).copy()).to(torch.int32)
+    s = b.sample_words(buf, words, pitch, seed=5, count=64)
+    assert s.shape == (words * pitch,) and np.array_equal(s, b.sample_words(buf, words, pitch, seed=5, count=64))
+    assert set(s.tolist()) <= {ww * 1000 + qq for ww in range(words) for qq in range(pitch)}
+    buf[0, 0, 0] = -2                               # int32 words read back as unsigned
+    assert b.sample_words(buf, 1, 1, seed=5, count=4).tolist() == [float(2 ** 32 - 2)]
+
+
 def test_box_record_parsing(monkeypatch):
     """The box record (bench.py box_identity / ClockSampler): the visible cards follow the
     HIP visibility list, and the medians under load parse rocm-smi's clock / power strings."""
