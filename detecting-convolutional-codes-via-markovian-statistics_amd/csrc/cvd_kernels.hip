@@ -2092,7 +2092,9 @@ struct CkPlan {
 };
 static int64_t round_up192(int64_t x) { return (x + 191) / 192 * 192; }
 // CVD_CHUNK: -1 (default) where it pays, 0 never, 1 wherever the kernel allows it (tests);
-// CVD_CHUNK_WARM (1152), CVD_CHUNK_UNITS (4 x the resident waves): warm-up steps and target units
+// CVD_CHUNK_WARM (1152), CVD_CHUNK_UNITS (4 x the resident waves): warm-up steps and target units;
+// tests only (ck_submit): CVD_CHUNK_REDO_ALL = 1 reruns every sequence, CVD_CHUNK_KAPPA_LOG2 = k
+// (0..45, default 0) widens the decision bound kappa by 2^k, which only adds exact reruns
 static bool ck_plan(const cvd_model& M, int64_t N, int64_t nseq_total, CkPlan* P) {
   const int mode = env_i("CVD_CHUNK", -1);
   if (mode == 0 || !M.rtc_fn || !M.rtc_bs || N <= 0 || N >= ((int64_t)1 << 30) || nseq_total <= 0) return false;
@@ -2201,8 +2203,10 @@ static int ck_submit(CkGroup& g, hipStream_t st) {
     HIP_CHECK(hipModuleLaunchKernel((hipFunction_t)M0.rtc_fn_multi, (unsigned)blocks, 1, 1, blk, 1, 1, lds, st, args,
                                     nullptr));
   }
-  const double kappa = 4.0 * (double)(g.N + g.P.L + g.P.C + 16) * 0x1p-53;
+  double kappa = 4.0 * (double)(g.N + g.P.L + g.P.C + 16) * 0x1p-53;
   const int32_t redo_all = env_i("CVD_CHUNK_REDO_ALL", 0);   // (tests: the rerun path for every sequence)
+  // (tests: a bound 2^k times wider sends more sequences to the exact rerun -- the near-tie branch)
+  kappa = std::ldexp(kappa, std::min(45, std::max(0, env_i("CVD_CHUNK_KAPPA_LOG2", 0))));
   for (int32_t i = 0; i < nm; ++i) {
     const unsigned grid = (unsigned)((g.nseq[i] + kBlock - 1) / kBlock);
     hipLaunchKernelGGL(ck_combine_kernel, dim3(grid), dim3(kBlock), 0, st, g.rec[i], g.nseq[i], g.nh1[i], g.P.C, kappa,
