@@ -14,19 +14,31 @@
       plots_compare.py:70-148 -- P_err = 1 - Pc of both detectors against p
       (per N) and against N (per p), one PNG each (host only, matplotlib)
 
+  ... scan --code C --p P --N N --input FILE [--format bytes|lsb|msb] [--nbits B]
+           [--start S] [--stride BITS] [--phases F] [--parity] [--gamma G] [--learn-len L]
+      (nothing in the reference) -- the detector over a captured bitstream: FILE is a
+      .npy of uint8 or a raw byte file, one bit per byte or packed LSB-/MSB-first; the
+      model of G1 is learned at the one crossover probability P; every window of N steps
+      from bit S, BITS apart (default N*n), at F candidate symbol phases, writes
+      <save-dir>/scan.csv with one row per (window, phase): window, phase, offset,
+      logp1, logref, llr, h1 (and parity_sat, parity_frac with --parity: the
+      parity-template baseline on the same windows).  Single-process: under torchrun
+      only rank 0 scans.
+
 Codes: the BASELINE configurations (m2, m6, r23_m4) or the demo presets
 (example:1, example:2, demo_script.py:35-52).  Every subcommand but compare
-runs on the GPU through libcvd.so.  Under torchrun (one process per GPU) the trials are
-sharded over the ranks, the counts reduced with one all_reduce, and rank 0
+runs on the GPU through libcvd.so.  Under torchrun (one process per GPU) the trials of
+experiment and parity are sharded over the ranks, the counts reduced with one all_reduce, and rank 0
 writes the CSV.
 """
 import argparse
+import csv
 import os
 import sys
 
 from . import (CONFIG_CODES, DEFAULTS, EXAMPLE_CODES, compute_error_exponent, default_template,
                learn_transition_tensor, parity_experiment, parity_vector_to_equation, parity_vectors,
-               run_experiment)
+               run_experiment, scan_capture)
 
 PROG = "python -m detecting-convolutional-codes-via-markovian-statistics_amd"
 
@@ -85,6 +97,27 @@ def parser():
     x.add_argument("--chains", type=int, default=1, help="independent chains (1: the reference's one chain)")
     x.add_argument("--u-grid", type=int, default=401)
 
+    s = sub.add_parser("scan", help="the detector over a captured bitstream")
+    s.add_argument("--code", default="example:1",
+                   help="m2 | m6 | r23_m4 (BASELINE configs) or example:1 | example:2 (demo presets)")
+    s.add_argument("--p", type=float, required=True, help="BSC crossover probability the model is learned at")
+    s.add_argument("--N", type=int, required=True, help="steps per window")
+    s.add_argument("--input", required=True, help=".npy of uint8, or a raw byte file")
+    s.add_argument("--format", choices=["bytes", "lsb", "msb"], default="bytes",
+                   help="one bit per byte, or packed with bit 0 / bit 7 of a byte first")
+    s.add_argument("--nbits", type=int, default=None, help="capture length in bits (default: the whole file)")
+    s.add_argument("--start", type=int, default=0, help="first capture bit of window 0")
+    s.add_argument("--stride", type=int, default=None, help="bits between windows (default N*n)")
+    s.add_argument("--phases", type=int, default=1, help="candidate symbol phases per window (1..n)")
+    s.add_argument("--parity", action="store_true", help="add the parity-template baseline's columns")
+    s.add_argument("--gamma", type=float, default=0.6, help="parity decision threshold (comp_parity.py:166)")
+    s.add_argument("--learn-len", type=int, default=DEFAULTS["learn_len"])
+    s.add_argument("--learn-burn", type=int, default=DEFAULTS["learn_burn"])
+    s.add_argument("--laplace", type=float, default=DEFAULTS["laplace"])
+    s.add_argument("--seed", type=int, default=DEFAULTS["seed"])
+    s.add_argument("--save-dir", default=DEFAULTS["save_dir"])
+    s.add_argument("--out", default=None, help="CSV path (default: <save-dir>/scan.csv)")
+
     c = sub.add_parser("compare", help="P_err figures of both detectors (plots_compare.py)")
     c.add_argument("--hybrid", required=True, help="CSV of the experiment subcommand")
     c.add_argument("--baseline", required=True, help="CSV of the parity subcommand")
@@ -133,8 +166,48 @@ def cmd_exponent(a):
     return pd.DataFrame(rows), "error_exponent.csv", "Error exponent (Eq. 7)"
 
 
+def load_capture(path):
+    """uint8 array of a capture file: a .npy of uint8, or the raw bytes of any other file."""
+    import numpy as np
+    if path.endswith(".npy"):
+        cap = np.load(path)
+        if cap.dtype != np.uint8:
+            raise SystemExit(f"{path}: a capture is uint8, not {cap.dtype}")
+        return cap.reshape(-1)
+    return np.fromfile(path, dtype=np.uint8)
+
+
+def cmd_scan(a):
+    """Writes the CSV; floats as repr, so they read back exactly."""
+    if int(os.environ.get("RANK", "0")) != 0:   # single-process: under torchrun rank 0 scans
+        return 0
+    k, n, m, g1, _ = code_of(a.code)
+    res = scan_capture(k, n, m, g1, load_capture(a.input), a.N, a.p, a.learn_len, a.learn_burn, a.laplace,
+                       a.seed, start=a.start, stride=a.stride, n_phase=a.phases, format=a.format, nbits=a.nbits,
+                       parity_template=default_template(g1, m) if a.parity else None, gamma=a.gamma)
+    cols = ["logp1", "logref", "llr"]
+    out = a.out or os.path.join(a.save_dir, "scan.csv")
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    nwin, nph = res["offset"].shape
+    with open(out, "w", newline="") as f:
+        wr = csv.writer(f)
+        wr.writerow(["window", "phase", "offset", *cols, "h1"] + (["parity_sat", "parity_frac"] if a.parity else []))
+        for i in range(nwin):
+            for ph in range(nph):
+                row = [i, ph, int(res["offset"][i, ph]), *[repr(float(res[c][i, ph])) for c in cols],
+                       int(res["h1"][i, ph])]
+                if a.parity:
+                    row += [int(res["parity_sat"][i, ph]), repr(float(res["parity_frac"][i, ph]))]
+                wr.writerow(row)
+    print(f"Scanned {nwin} windows x {nph} phases: {int(res['h1'].sum())} decided H1")
+    print("Saved results to", out)
+    return 0
+
+
 def main(argv=None):
     a = parser().parse_args(argv)
+    if a.cmd == "scan":
+        return cmd_scan(a)
     if a.cmd == "compare":
         from .compare import compare_figures
         for path in compare_figures(a.hybrid, a.baseline, a.outdir):

@@ -17,6 +17,10 @@ ABI_VERSION = 11
 
 PATH_AUTO, PATH_TABLE, PATH_EXPLICIT, PATH_EXPLICIT_GENERIC, PATH_EXPLICIT_ORBIT, PATH_EXPLICIT_BUTTERFLY = 0, 1, 2, 3, 4, 5
 DETECT_EARLY_DECISION = 0x100   # OR'ed into path: counts only, stop once every decision is certain
+# capture bit order (cvd_pack_windows): bit b = bit b & 7 of byte b >> 3 / bit 7 - (b & 7) of it
+# (numpy.packbits default) / byte[b] & 1 (one bit per byte)
+CAPTURE_LSB, CAPTURE_MSB, CAPTURE_BYTES = 0, 1, 2
+CAPTURE_FORMATS = {"lsb": CAPTURE_LSB, "msb": CAPTURE_MSB, "bytes": CAPTURE_BYTES}
 
 
 class CvdError(RuntimeError):
@@ -91,6 +95,10 @@ EXPORTS = {
                                     ctypes.c_double, ctypes.c_int64, ctypes.c_int32, ctypes.c_int64,
                                     ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
                                     ctypes.c_int64, ctypes.c_void_p]),
+    "cvd_pack_windows": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
+                                        ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                                        ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
+                                        ctypes.c_void_p]),
     "cvd_detect": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
                                   ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32,
                                   ctypes.c_void_p]),

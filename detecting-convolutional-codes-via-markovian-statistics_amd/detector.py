@@ -354,6 +354,116 @@ class Detector:
                                         ctypes.c_void_p(D.data_ptr()), _stream_ptr(stream)))
         return D
 
+    # ── captured bitstreams (cvd_pack_windows) ──────────────────────────────
+
+    def _capture_buffer(self, capture, format, nbits):
+        """(device uint8 tensor readable to a multiple of 16 bytes, format code, nbits) of a
+        capture given as a numpy array or torch tensor of uint8 (packed bytes, or one bit
+        per byte).  A host array is uploaded padded to 16 bytes; a device tensor is used in
+        place when its length already is a multiple of 16."""
+        if format not in _lib.CAPTURE_FORMATS:
+            raise ValueError(f"capture format {format!r}: one of {', '.join(_lib.CAPTURE_FORMATS)}")
+        fmt = _lib.CAPTURE_FORMATS[format]
+        cap = torch.from_numpy(np.ascontiguousarray(capture)) if isinstance(capture, np.ndarray) else capture
+        if not isinstance(cap, torch.Tensor) or cap.dtype != torch.uint8:
+            raise TypeError("a capture is a numpy array or torch tensor of uint8")
+        cap = cap.reshape(-1)
+        nbytes = cap.numel()
+        have = nbytes if fmt == _lib.CAPTURE_BYTES else 8 * nbytes
+        nbits = have if nbits is None else int(nbits)
+        if not 0 <= nbits <= have:
+            raise ValueError(f"nbits = {nbits} outside the capture's {have} bits")
+        if cap.device != self.device or not cap.is_contiguous() or nbytes % 16 or cap.data_ptr() % 16:
+            buf = torch.zeros((nbytes + 15) // 16 * 16 or 16, dtype=torch.uint8, device=self.device)
+            buf[:nbytes].copy_(cap)
+            cap = buf
+        return cap, fmt, nbits
+
+    def windows_in(self, nbits, N, start=0, stride=None, n_phase=1):
+        """Whole windows of N steps, every one of its n_phase phases included, that fit in
+        capture bits [start, nbits) at `stride` bits apart (default N*n)."""
+        stride = int(N) * self.n if stride is None else int(stride)
+        if stride <= 0:
+            raise ValueError("stride must be a positive number of bits")
+        room = int(nbits) - int(start) - (int(n_phase) - 1) - int(N) * self.n
+        return room // stride + 1 if room >= 0 else 0
+
+    def pack_capture(self, capture, N, start=0, stride=None, n_phase=1, nwin=None, format="bytes", nbits=None,
+                     out=None, q0=0, pitch=None, stream=None):
+        """Windows of a captured serial bitstream as a received-word buffer (cvd_pack_windows):
+        window i, phase f starts at capture bit start + i*stride + f, holds N steps and
+        becomes sequence q0 + i*n_phase + f of the buffer [W/4, pitch, 4] (include/cvd.h
+        layout), which detect(), trace() and parity_detect() read.  stride=None: N*n bits
+        (non-overlapping windows); nwin=None: as many whole windows as fit; nbits: the
+        capture's length in bits (default: all of the array).  Returns (buffer, nwin)."""
+        cap, fmt, nbits = self._capture_buffer(capture, format, nbits)
+        stride = int(N) * self.n if stride is None else int(stride)
+        if nwin is None:
+            nwin = self.windows_in(nbits, N, start, stride, n_phase)
+        nseq = int(nwin) * int(n_phase)
+        pitch = int(q0) + nseq if pitch is None else int(pitch)
+        if out is None:
+            out = self.stream_buffer(N, max(pitch, 1))
+        _lib.check(_lib.lib().cvd_pack_windows(ctypes.c_void_p(cap.data_ptr()), nbits, fmt, self.n, int(N),
+                                               int(start), stride, int(nwin), int(n_phase),
+                                               ctypes.c_void_p(out.data_ptr()), pitch, int(q0),
+                                               _stream_ptr(stream)))
+        return out, int(nwin)
+
+    def scan(self, model, capture, N, start=0, stride=None, n_phase=1, format="bytes", nbits=None,
+             parity_template=None, gamma=0.6, batch=None, path=_lib.PATH_AUTO):
+        """The detector over a captured bitstream: every window of N steps from capture bit
+        `start`, `stride` bits apart (default N*n), at n_phase candidate symbol phases.
+        Returns numpy arrays [nwin, n_phase]: offset (the window's first capture bit), logp1
+        and logref (cvd_detect's sequential fp64 sums, Pd_plotter.py:106-116), llr = logp1 -
+        logref, h1 = logp1 > logref (the H1 decision, Pd_plotter.py:215); best_phase [nwin] =
+        argmax of llr over the phases; with parity_template also parity_sat (satisfied
+        anchors) and parity_frac (comp_parity.py:90-117) of the same packed windows.
+        batch: windows per launch (default: sized from free memory, as default_batch).  The
+        capture itself must fit in device memory."""
+        cap, fmt, nbits = self._capture_buffer(capture, format, nbits)
+        n_phase = int(n_phase)
+        stride = int(N) * self.n if stride is None else int(stride)
+        nwin = self.windows_in(nbits, N, start, stride, n_phase)
+        if batch is None:
+            free, _ = torch.cuda.mem_get_info(self.device)
+            per_win = n_phase * (self.words_per_seq(N) * 4 + 32)
+            batch = max(1, min(free // 3, 96 << 30) // per_win)
+        batch = max(1, min(int(batch), max(nwin, 1)))
+        sums = np.zeros((nwin * n_phase, 2))
+        sat = np.zeros(nwin * n_phase, np.int64)
+        counts = torch.zeros(2, dtype=torch.int64, device=self.device)
+        if parity_template is not None:
+            from .parity import parity_detect
+        for w0 in range(0, nwin, batch):
+            nb = min(batch, nwin - w0)
+            nseq = nb * n_phase
+            # one buffer per batch with pitch = its sequences (cvd_detect: pitch = nseq)
+            r, _ = self.pack_capture(cap, N, int(start) + w0 * stride, stride, n_phase, nb,
+                                     format=format, nbits=nbits)
+            # NaN-filled, as in run_trials: an unwritten sequence cannot pass for a result
+            d_sums = torch.full((nseq, 2), float("nan"), dtype=torch.float64, device=self.device)
+            self.detect(model, r, N, nseq, nseq, sums=d_sums, counts=counts, path=path)
+            sums[w0 * n_phase:w0 * n_phase + nseq] = d_sums.cpu().numpy()
+            if parity_template is not None:
+                d_sat = torch.zeros(nseq, dtype=torch.int32, device=self.device)
+                parity_detect(r, self.n, N, nseq, nseq, parity_template, gamma, sat=d_sat)
+                sat[w0 * n_phase:w0 * n_phase + nseq] = d_sat.cpu().numpy()
+        model.device_error()
+        sums = sums.reshape(nwin, n_phase, 2)
+        logp1, logref = sums[..., 0].copy(), sums[..., 1].copy()
+        llr = logp1 - logref
+        res = {"offset": int(start) + np.arange(nwin, dtype=np.int64)[:, None] * stride
+                         + np.arange(n_phase, dtype=np.int64)[None, :],
+               "logp1": logp1, "logref": logref, "llr": llr, "h1": logp1 > logref,
+               "best_phase": np.argmax(llr, axis=1) if nwin else np.zeros(0, np.int64)}
+        if parity_template is not None:
+            first = max(s for (_, s) in parity_template)
+            total = int(N) - first if int(N) > first else 0
+            res["parity_sat"] = sat.reshape(nwin, n_phase)
+            res["parity_frac"] = res["parity_sat"] / total if total > 0 else np.zeros((nwin, n_phase))
+        return res
+
     # one residency round of the butterfly kernel: 4 waves/SIMD x 1024 SIMDs x 64
     # lanes = 262,144 sequences = 131,072 trials (H1 + H2)
     FULL_ROUND_TRIALS = 131_072
@@ -550,6 +660,17 @@ def run_experiment(k, n, m, gen1, gen2, num_iter, p_vec, learn_len, learn_burn, 
     for mdl in models:
         mdl.device_error()
     return pd.DataFrame(pd_rows(counts, N_spectrum, list(p_vec), num_iter))
+
+
+def scan_capture(k, n, m, gen1, capture, N, p, learn_len=None, learn_burn=200, laplace=1.0, seed=12345,
+                 device=None, **scan_kw):
+    """Detector.scan in one call: the detector of G1 and its model learned at crossover
+    probability p, as run_experiment gets them, over a captured bitstream (nothing in the
+    reference: its streams all come from its own simulator).  scan_kw: start, stride,
+    n_phase, format, nbits, parity_template, gamma, batch, path."""
+    det = _detector(k, n, m, gen1, device)
+    model = det.prepare_models([p], learn_len, learn_burn, laplace, seed)[0]
+    return det.scan(model, capture, N, **scan_kw)
 
 
 def learn_P1_empirical(gens_tuple, k, n, m, p, learn_len, learn_burn, laplace, seed):

@@ -19,6 +19,8 @@
  *   (none: the reference is single-process)                                        cvd_allreduce_counts / cvd_comm_* (RCCL)
  *   comp_parity.py:90-128     parity_satisfaction_fraction / parity_detector       cvd_parity_detect
  *                             (parity-template baseline)
+ *   (none: the reference detects only streams it simulated)                        cvd_pack_windows
+ *                             (a captured serial bitstream cut into windows in cvd_generate's layout)
  *   alpha_exponent.py:83-156  learn_transition_tensor (joint counts)              cvd_count_transitions
  *   alpha_exponent.py:159-188 compute_error_exponent: M(u) for a u grid           cvd_chernoff_build(_dense)
  *   alpha_exponent.py:69-76   spectral_radius (Perron root of M(u) >= 0)           cvd_spectral_radius
@@ -201,8 +203,36 @@ int cvd_generate(const cvd_code* enc, uint64_t seed, uint32_t tag, double p, int
                  int32_t random_input, int64_t seq_base, int64_t seq_stride,
                  uint32_t* d_r, int64_t pitch, int64_t q0, int64_t count, void* stream);
 
+/* Captured bitstream -> received-word buffer: the way in for streams cvd_generate did not
+ * make (a demodulator's hard decisions; nothing in the reference, whose streams all come
+ * from its own simulator).  The capture is the serial channel stream in device memory:
+ * relative to a window's first bit, bit n*t + j is output j of step t.  Window i, phase f
+ * (0 <= f < n_phase <= n: the candidate symbol phases) begins at capture bit
+ * start + i*stride + f, holds N steps (N*n bits) and becomes sequence
+ * q = q0 + i*n_phase + f of d_r in exactly cvd_generate's layout: W = ceil(N / floor(32/n))
+ * words, step t in bits [n*(t % SPW), +n) of word t / SPW (SPW = floor(32/n)), word w at
+ * d_r[((w/4)*pitch + q)*4 + w%4]; the bits of the last word past step N and the padding
+ * words up to a multiple of 4 are zero.  Columns of d_r outside [q0, q0 + nwin*n_phase) are
+ * not written.  stride: any positive number of bits (stride < N*n: overlapping windows).
+ * Bit b of the capture, by format: */
+#define CVD_CAPTURE_LSB   0  /* bit b of the capture = bit (b & 7) of byte b >> 3 */
+#define CVD_CAPTURE_MSB   1  /* bit b = bit 7 - (b & 7) of byte b >> 3 (numpy.packbits default) */
+#define CVD_CAPTURE_BYTES 2  /* one bit per byte: bit b = byte[b] & 1 */
+/* d_capture (and d_r) 16-byte aligned; the capture readable up to its byte length
+ * (ceil(nbits/8), or nbits for CVD_CAPTURE_BYTES) rounded up to 16: the kernel never reads
+ * at or past that, and bits at index >= nbits never reach the output.  Bit positions are
+ * 64-bit throughout (a capture may exceed 2^32 bits).  CVD_E_INVALID, without touching the
+ * device, for: n outside 1..3, n_phase outside 1..n, N < 0, start < 0, stride <= 0,
+ * nwin < 0, an unknown format, q0 < 0, pitch < q0 + nwin*n_phase, a window not entirely
+ * inside [0, nbits), or any of these products overflowing int64.  nwin == 0 or N == 0:
+ * CVD_OK without a launch.  Asynchronous on `stream`, like cvd_generate. */
+int cvd_pack_windows(const void* d_capture, int64_t nbits, int32_t format,
+                     int32_t n, int64_t N,
+                     int64_t start, int64_t stride, int64_t nwin, int32_t n_phase,
+                     uint32_t* d_r, int64_t pitch, int64_t q0, void* stream);
+
 #define CVD_PATH_AUTO 0
-#define CVD_PATH_TABLE 1     /* enumerated state automaton (dense models) */
+#define CVD_PATH_TABLE 1    /* enumerated state automaton (dense models) */
 #define CVD_PATH_EXPLICIT 2  /* explicit 2^m metric vector + hashed P̂1 rows (fastest k=1 kernel that applies) */
 #define CVD_PATH_EXPLICIT_GENERIC 3  /* explicit path, ACS for every received word (no orbit reduction) */
 #define CVD_PATH_EXPLICIT_ORBIT 4    /* explicit path, k=1 two-representative orbit kernel */
