@@ -10,12 +10,15 @@ from .detector import (  # noqa: F401
     DEFAULTS, N_SPECTRUM_BY_M, Detector, Model, run_experiment, learn_P1_empirical,
     enumerate_markov_states_allzero, build_trellis, branch_output_and_next_state,
     viterbi_metric_step, simulate_markov_sequence, log_likelihood_ratio, grid_tag, LEARN_TAG,
-    enumerate_states_device, scan_capture,
+    enumerate_states_device, scan_capture, capture_buffer,
 )
 from .parity import (  # noqa: F401
     parse_poly_token, build_parity_system, nullspace_mod2, parity_vector_to_equation, parity_vectors,
     template_of, default_template, parity_detect, parity_satisfaction_fraction, parity_detector,
     parity_experiment,
+)
+from .blind import (  # noqa: F401
+    template_mask, mask_template, mask_extent, parity_sweep, find_parity_checks, identify_code, default_z_min,
 )
 from .exponent import (  # noqa: F401
     TransitionTensor, learn_transition_tensor, chernoff_rhos, compute_error_exponent, spectral_radius,

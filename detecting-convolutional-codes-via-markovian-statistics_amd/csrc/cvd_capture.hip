@@ -28,6 +28,7 @@
 #include <string>
 
 #include "../../include/cvd.h"
+#include "cvd_capture_bits.h"
 #include "cvd_internal.h"
 
 namespace {
@@ -54,17 +55,6 @@ struct PackArgs {
   int64_t ctiles;       // tiles along a window: ceil(nchunks / kChunks)
   int64_t block0;       // first block of this launch
 };
-
-// per-byte bit reversal: MSB-first bytes -> LSB-first
-__device__ __forceinline__ uint32_t lsb_first(uint32_t x) { return __builtin_bswap32(__builtin_bitreverse32(x)); }
-
-// bit 0 of each of a dword's four bytes -> bits 0..3
-__device__ __forceinline__ uint32_t byte_bits4(uint32_t x) {
-  x &= 0x01010101u;
-  x |= x >> 7;
-  x |= x >> 14;
-  return x & 0xFu;
-}
 
 template <int n, int format>
 __global__ __launch_bounds__(kBlock) void pack_windows_kernel(PackArgs a) {

@@ -64,6 +64,30 @@ def _stream_ptr(stream=None):
     return ctypes.c_void_p(s.cuda_stream)
 
 
+def capture_buffer(capture, format, nbits, device):
+    """(device uint8 tensor readable to a multiple of 16 bytes, format code, nbits) of a
+    capture given as a numpy array or torch tensor of uint8 (packed bytes, or one bit per
+    byte).  A host array is uploaded padded to 16 bytes; a tensor on `device` is used in
+    place when its length already is a multiple of 16."""
+    if format not in _lib.CAPTURE_FORMATS:
+        raise ValueError(f"capture format {format!r}: one of {', '.join(_lib.CAPTURE_FORMATS)}")
+    fmt = _lib.CAPTURE_FORMATS[format]
+    cap = torch.from_numpy(np.ascontiguousarray(capture)) if isinstance(capture, np.ndarray) else capture
+    if not isinstance(cap, torch.Tensor) or cap.dtype != torch.uint8:
+        raise TypeError("a capture is a numpy array or torch tensor of uint8")
+    cap = cap.reshape(-1)
+    nbytes = cap.numel()
+    have = nbytes if fmt == _lib.CAPTURE_BYTES else 8 * nbytes
+    nbits = have if nbits is None else int(nbits)
+    if not 0 <= nbits <= have:
+        raise ValueError(f"nbits = {nbits} outside the capture's {have} bits")
+    if cap.device != device or not cap.is_contiguous() or nbytes % 16 or cap.data_ptr() % 16:
+        buf = torch.zeros((nbytes + 15) // 16 * 16 or 16, dtype=torch.uint8, device=device)
+        buf[:nbytes].copy_(cap)
+        cap = buf
+    return cap, fmt, nbits
+
+
 def model_cache_dir(explicit=None):
     """Directory of the on-disk model cache: `explicit`, else $CVD_MODEL_CACHE; None
     (no cache) when neither is set or the value is "off"."""
@@ -361,23 +385,7 @@ class Detector:
         capture given as a numpy array or torch tensor of uint8 (packed bytes, or one bit
         per byte).  A host array is uploaded padded to 16 bytes; a device tensor is used in
         place when its length already is a multiple of 16."""
-        if format not in _lib.CAPTURE_FORMATS:
-            raise ValueError(f"capture format {format!r}: one of {', '.join(_lib.CAPTURE_FORMATS)}")
-        fmt = _lib.CAPTURE_FORMATS[format]
-        cap = torch.from_numpy(np.ascontiguousarray(capture)) if isinstance(capture, np.ndarray) else capture
-        if not isinstance(cap, torch.Tensor) or cap.dtype != torch.uint8:
-            raise TypeError("a capture is a numpy array or torch tensor of uint8")
-        cap = cap.reshape(-1)
-        nbytes = cap.numel()
-        have = nbytes if fmt == _lib.CAPTURE_BYTES else 8 * nbytes
-        nbits = have if nbits is None else int(nbits)
-        if not 0 <= nbits <= have:
-            raise ValueError(f"nbits = {nbits} outside the capture's {have} bits")
-        if cap.device != self.device or not cap.is_contiguous() or nbytes % 16 or cap.data_ptr() % 16:
-            buf = torch.zeros((nbytes + 15) // 16 * 16 or 16, dtype=torch.uint8, device=self.device)
-            buf[:nbytes].copy_(cap)
-            cap = buf
-        return cap, fmt, nbits
+        return capture_buffer(capture, format, nbits, self.device)
 
     def windows_in(self, nbits, N, start=0, stride=None, n_phase=1):
         """Whole windows of N steps, every one of its n_phase phases included, that fit in

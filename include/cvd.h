@@ -21,6 +21,8 @@
  *                             (parity-template baseline)
  *   (none: the reference detects only streams it simulated)                        cvd_pack_windows
  *                             (a captured serial bitstream cut into windows in cvd_generate's layout)
+ *   (none: the reference's templates come from known generators)                   cvd_parity_sweep
+ *                             (all 2^B parity templates of a capture at once: histogram + WHT)
  *   alpha_exponent.py:83-156  learn_transition_tensor (joint counts)              cvd_count_transitions
  *   alpha_exponent.py:159-188 compute_error_exponent: M(u) for a u grid           cvd_chernoff_build(_dense)
  *   alpha_exponent.py:69-76   spectral_radius (Perron root of M(u) >= 0)           cvd_spectral_radius
@@ -385,6 +387,37 @@ void cvd_comm_destroy(cvd_comm* comm);
 int cvd_parity_detect(const uint32_t* d_r, int32_t n, int64_t N, int64_t nseq, int64_t n_h1,
                       const int32_t* terms, int32_t n_terms, double gamma, int32_t* d_sat,
                       int64_t* d_counts, void* stream);
+
+/* ---- blind parity-check sweep of a capture (nothing in the reference) --------
+ * Which parity checks does a captured stream satisfy, and at which symbol phase?  Every
+ * one of the 2^B templates over a window of span + 1 symbols, B = n*(span+1), is tested at
+ * once: one histogram of the B-bit words the window sees and one Walsh-Hadamard transform,
+ *   sat[mask] = (T + sum_x hist[x] * (-1)^popcount(mask & x)) / 2.
+ * The capture, `format`, the alignment and 16-byte readability rule of d_capture and the
+ * 64-bit bit positions are exactly those of cvd_pack_windows.  1 <= B <= 22.  Anchor a
+ * (0 <= a < T) at phase f (0 <= f < n_phase <= n) has the word x whose bit i (i < B) is
+ * capture bit start + f + n*a + i: bit n*e + j of x is output j of symbol a + e, and the
+ * template term (output j, delay s) of cvd_parity_detect is mask bit n*(span - s) + j.
+ *   d_sat[f*2^B + mask] += #{a : popcount(mask & x) even}      (int64 [n_phase][2^B])
+ * accumulated, not cleared, like d_counts: sat[f][0] grows by T, and two calls over
+ * adjacent anchor ranges equal one call over both.  Integer only: the result does not
+ * depend on launch shape or on the order atomics arrive in.  d_work: the histogram
+ * workspace, cvd_parity_sweep_workspace_bytes(n, span, n_phase) bytes (n_phase * 2^B * 4;
+ * < 0 with the error set for an invalid shape), 16-byte aligned; the call zeroes it on
+ * `stream`.  d_sat 8-byte aligned.  Asynchronous on `stream`.
+ * CVD_E_INVALID, before the device is touched, for: n outside 1..3, span < 0, B > 22,
+ * n_phase outside 1..n, T < 0 or T > 2^31 - 1, start < 0, nbits < 0, an unknown format,
+ * the last word not inside [0, nbits) (start + (n_phase-1) + n*(T-1) + B > nbits), an
+ * int64 overflow in these products, and null or misaligned pointers when T > 0.
+ * T == 0: CVD_OK without a launch.  The block-local histogram lives in LDS up to B = 15
+ * and the transform of a phase then runs in one block; B = 16..21 counts 2^15-bin parts of
+ * the histogram in LDS, B = 22 uses global atomics, both with a two-pass tiled transform
+ * (csrc/cvd_sweep.hip; CVD_SWEEP_GLOBAL_B = the smallest B on global
+ * atomics, >= 16, for A/B runs: the result is the same). */
+int64_t cvd_parity_sweep_workspace_bytes(int32_t n, int32_t span, int32_t n_phase);
+int cvd_parity_sweep(const void* d_capture, int64_t nbits, int32_t format, int32_t n, int32_t span,
+                     int64_t start, int64_t T, int32_t n_phase, int64_t* d_sat, void* d_work,
+                     void* stream);
 
 /* ---- error-exponent engine (alpha_exponent.py, Eq. 7) ---------------------
  * Joint counts of (metric state i, received word r) along received streams
