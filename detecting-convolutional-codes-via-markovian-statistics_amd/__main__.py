@@ -33,6 +33,16 @@
       per check: rank, phase, mask (hex), extent, sat, T, z, equation.  For N = 2 the
       first check is the generator pair: printed in octal with the scan --code line that
       takes it.  Single-process, like scan.
+  ... decode --code C --input FILE [--format bytes|lsb|msb] [--nbits B] [--start S] [--T T]
+             [--out-bits FILE.npy]
+      (nothing in the reference) -- what was sent: the hard-decision Viterbi decoder of the
+      k = 1 code C over the capture from bit S (cvd_viterbi_decode: the Eq. 4-5 recursion with
+      its survivor decisions kept, exact whatever the block split); writes the decoded bits to
+      <save-dir>/decoded.npy (uint8, packed LSB-first: a --format lsb --nbits T capture that
+      identify takes, e.g. for an outer code) and a one-row <save-dir>/decode.csv: T, errors,
+      ber, start_state, end_state, blocks, forward_reruns, trace_fixups.  ber = errors / (n T)
+      estimates the channel's crossover probability: printed with the scan line that takes
+      it, so the workflow is identify -> decode -> scan.  Single-process, like scan.
 
 Codes: the BASELINE configurations (m2, m6, r23_m4), the demo presets (example:1,
 example:2, demo_script.py:35-52), or oct:G0,G1[,G2] -- k = 1 generators in octal (MSB =
@@ -49,7 +59,7 @@ import re
 import sys
 
 from . import (CONFIG_CODES, DEFAULTS, EXAMPLE_CODES, compute_error_exponent, default_template,
-               find_parity_checks, learn_transition_tensor, octal_to_taps, parity_experiment,
+               decode_capture, find_parity_checks, learn_transition_tensor, octal_to_taps, parity_experiment,
                parity_vector_to_equation, parity_vectors, run_experiment, scan_capture)
 
 PROG = "python -m detecting-convolutional-codes-via-markovian-statistics_amd"
@@ -157,6 +167,19 @@ def parser():
     i.add_argument("--top", type=int, default=16, help="checks listed")
     i.add_argument("--save-dir", default=DEFAULTS["save_dir"])
     i.add_argument("--out", default=None, help="CSV path (default: <save-dir>/identify.csv)")
+
+    d = sub.add_parser("decode", help="hard-decision Viterbi decoder of a captured bitstream")
+    d.add_argument("--code", required=True,
+                   help="m2 | m6 (BASELINE configs), example:1 | example:2 (demo presets) or oct:133,171 (k = 1)")
+    d.add_argument("--input", required=True, help=".npy of uint8, or a raw byte file")
+    d.add_argument("--format", choices=["bytes", "lsb", "msb"], default="bytes",
+                   help="one bit per byte, or packed with bit 0 / bit 7 of a byte first")
+    d.add_argument("--nbits", type=int, default=None, help="capture length in bits (default: the whole file)")
+    d.add_argument("--start", type=int, default=0, help="capture bit of output 0 of step 0")
+    d.add_argument("--T", type=int, default=None, help="steps to decode (default: as many whole symbols as fit)")
+    d.add_argument("--out-bits", default=None, help=".npy path of the decoded bits (default: <save-dir>/decoded.npy)")
+    d.add_argument("--save-dir", default=DEFAULTS["save_dir"])
+    d.add_argument("--out", default=None, help="CSV path (default: <save-dir>/decode.csv)")
 
     c = sub.add_parser("compare", help="P_err figures of both detectors (plots_compare.py)")
     c.add_argument("--hybrid", required=True, help="CSV of the experiment subcommand")
@@ -281,8 +304,42 @@ def cmd_identify(a):
     return 0
 
 
+DECODE_COLUMNS = ["T", "errors", "ber", "start_state", "end_state", "blocks", "forward_reruns", "trace_fixups"]
+
+
+def cmd_decode(a):
+    """Writes the bits and the one-row CSV; ber as repr, so it reads back exactly."""
+    if int(os.environ.get("RANK", "0")) != 0:   # single-process: under torchrun rank 0 decodes
+        return 0
+    import numpy as np
+    k, n, m, g1, _ = code_of(a.code)
+    if k != 1:
+        raise SystemExit(f"decode: {a.code} has k = {k}; the decoder takes k = 1 codes")
+    res = decode_capture(n, m, g1, load_capture(a.input), start=a.start, T=a.T, format=a.format, nbits=a.nbits)
+    out = a.out or os.path.join(a.save_dir, "decode.csv")
+    out_bits = a.out_bits or os.path.join(a.save_dir, "decoded.npy")
+    for path in (out, out_bits):
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(out_bits, "wb") as f:             # (np.save would append .npy to another suffix)
+        np.save(f, res["bits"].cpu().numpy())
+    with open(out, "w", newline="") as f:
+        wr = csv.writer(f)
+        wr.writerow(DECODE_COLUMNS)
+        wr.writerow([repr(res[c]) if c == "ber" else res[c] for c in DECODE_COLUMNS])
+    print(f"Decoded {res['T']} steps: {res['errors']} channel errors, p = {res['ber']!r} "
+          f"(states {res['start_state']} -> {res['end_state']}; {res['blocks']} blocks, "
+          f"{res['forward_reruns']} forward reruns, {res['trace_fixups']} traceback fix-ups)")
+    print(f"{PROG} scan --code {a.code} --start {a.start} --input {a.input} --format {a.format}"
+          + (f" --nbits {a.nbits}" if a.nbits is not None else "") + f" --p {res['ber']!r} --N N")
+    print("Saved bits to", out_bits, "(identify --format lsb --nbits", str(res["T"]) + ")")
+    print("Saved results to", out)
+    return 0
+
+
 def main(argv=None):
     a = parser().parse_args(argv)
+    if a.cmd == "decode":
+        return cmd_decode(a)
     if a.cmd == "scan":
         return cmd_scan(a)
     if a.cmd == "identify":

@@ -1,0 +1,627 @@
+// Hard-decision Viterbi decoder of a captured bitstream (cvd_viterbi_decode, include/cvd.h)
+// for gfx950: the Eq. 4-5 recursion of the detector with its survivor decisions kept, cut
+// into blocks of L steps that run in parallel, and exact: the result is the sequential
+// decoder's whatever the split.  Speculative work counts only where it is certified.
+//
+//   forward   one wavefront per block b.  It starts W steps early from D = 0, stores the
+//             relative metric vector it reaches at step bL (the warm vector), then runs the
+//             block's L steps recording per step the 2^m-bit decision word (__ballot of
+//             "predecessor b = 1 strictly smaller") and stores the relative vector at the
+//             block's end and the amount it was normalised by.  Lane = next state (2^m < 64:
+//             the upper lanes repeat states and are masked out of the ballot; 2^m = 128, 256:
+//             two / four states per lane).  The predecessor metrics come over ds_bpermute for
+//             2^m <= 64 and through a double-buffered LDS vector above; metrics are plain
+//             ints normalised at the two block edges only (the decisions do not depend on
+//             the common offset; n (L + W) is far from overflow).  The received symbols are
+//             staged 1,024 steps at a time into LDS as LSB-first dwords (cvd_capture_bits.h)
+//             and shifted out of an SGPR pair; the branch metrics of a lane's two branches
+//             for every y sit in 2-bit fields of two registers.  Lane j keeps the decision
+//             word of a 64-step chunk's step j and every 64 steps the wave stores 64 of them
+//             in one contiguous piece.
+//   compare   a thread per block: does the warm vector of b equal the end vector of b - 1?
+//   join      one wave walks the mismatch flags in ascending order; where the true vector
+//             at bL (in registers after a rerun, else the stored end vector of b - 1) differs
+//             from the warm vector of b it reruns block b from the true vector, rewriting its
+//             decisions, end vector and normalisation, and goes on to b + 1 (a cascade ends
+//             at the first block whose warm vector was right).
+//   look      one wave per block.  D lookahead steps with lane = state, each lane following
+//             its own survivor back from step e = min(T, (b+1)L + D); if all of them sit in
+//             one state at (b+1)L the block is certified to trace from that state (e = T:
+//             from the true end state, followed back to (b+1)L).  64 steps at a time: lane j
+//             loads the decision word of step base + j (one contiguous piece), the chain
+//             reads them with v_readlane.
+//   trace     the certified blocks' L-step chains, lane = block: 64 independent chains per
+//             wave, each lane reading its own decision words a 128-byte line at a time with
+//             the next line in flight (one wave per block, every lane on the same chain,
+//             measured 2.9 ms of the 8.0 ms of 2^27 steps; this way 0.5 ms).
+//             A block owns whole output words (32 | L).
+//   fix       one wave resolves the uncertified blocks in descending order from the start
+//             state the block after them traced (the chain in SGPRs, on the scalar unit),
+//             and writes d_stats.
+// The channel-error count is the path metric of the traced path: the sum of the blocks'
+// normalisations (D_0 = 0 and D_T(s_T) = 0, and along the decisions D'(s') = D(ps) + d_H
+// holds exactly), integer adds in any order.  No scratch.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <string>
+
+#include "../../include/cvd.h"
+#include "cvd_capture_bits.h"
+#include "cvd_internal.h"
+
+namespace {
+
+constexpr int kWave = 64;
+constexpr int kSeg = 1024;                   // steps staged at once (a multiple of 64)
+constexpr int kStageDw = 3 * kSeg / 32 + 4;  // n <= 3: the segment's dwords, alignment slack, funnel word
+
+template <int m>
+struct Shape {
+  static constexpr int S = 1 << m;
+  static constexpr int SPL = S > kWave ? S / kWave : 1;   // states per lane = 64-bit words per decision
+};
+
+struct VArgs {
+  const uint4* cap;
+  int64_t nu4;            // readable 16-byte pieces of the capture
+  int32_t format;
+  int64_t start, T;
+  int32_t L, W, D;
+  int64_t nb;
+  uint32_t gs[3];         // output j: taps of delays 1..m as a mask over the state
+  uint32_t g0;            // bit j: tap of delay 0 of output j
+  uint64_t* dec;          // [nb L][SPL] decision words
+  uint8_t* warm;          // [nb][S]
+  uint8_t* endv;          // [nb][S]
+  int32_t* norm;          // [nb] min of the block's unnormalised end vector
+  int32_t* sst;           // [nb] traced state at step bL
+  int32_t* xs;            // [nb] state at step (b+1)L that block b traces from (certified blocks)
+  int32_t* mis;           // [nb] warm vector of b != forward pass's end vector of b - 1
+  int32_t* unc;           // [nb] block not certified by its lookahead
+  unsigned long long* cnt;  // errors, forward reruns, traceback fix-ups
+  uint32_t* bits;
+  int64_t* stats;
+};
+
+// capture bits [start + n t0, + n cnt) as LSB-first dwords from the dword that holds the first
+template <int n>
+__device__ __forceinline__ void stage_bits(const VArgs& a, int64_t t0, int cnt, uint32_t* st, int lane) {
+  const int64_t p0 = a.start + (int64_t)n * t0;
+  const int64_t g0 = p0 >> 5;
+  const int ndw = ((int)(p0 & 31) + n * cnt + 31) / 32 + 1;    // <= kStageDw
+  for (int i = lane; i < ndw; i += kWave) {
+    const int64_t g = g0 + i;
+    uint32_t v = 0u;
+    if (a.format != CVD_CAPTURE_BYTES) {
+      if ((g >> 2) < a.nu4) {
+        v = reinterpret_cast<const uint32_t*>(a.cap)[g];
+        if (a.format == CVD_CAPTURE_MSB) v = lsb_first(v);
+      }
+    } else {
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const int64_t piece = 2 * g + h;
+        if (piece < a.nu4) {
+          const uint4 u = a.cap[piece];
+          v |= (byte_bits4(u.x) | (byte_bits4(u.y) << 4) | (byte_bits4(u.z) << 8) | (byte_bits4(u.w) << 12)) << (16 * h);
+        }
+      }
+    }
+    st[i] = v;
+  }
+}
+
+template <int m, int n>
+struct Lane {
+  static constexpr int S = Shape<m>::S, SPL = Shape<m>::SPL;
+  int lane;
+  int ps0[SPL], ps1[SPL];          // predecessors of the lane's next states
+  uint32_t bm0[SPL], bm1[SPL];     // their branch metrics: bits 2y..2y+1 = d_H(out(ps_b, u), y)
+
+  __device__ __forceinline__ int state(int i) const { return (lane & (S - 1)) + kWave * i; }
+
+  __device__ __forceinline__ void init(const VArgs& a) {
+    lane = threadIdx.x;
+#pragma unroll
+    for (int i = 0; i < SPL; ++i) {
+      const int s = state(i), u = s & 1;
+      ps0[i] = s >> 1;
+      ps1[i] = ps0[i] | (1 << (m - 1));
+      uint32_t o0 = 0u, o1 = 0u;
+#pragma unroll
+      for (int j = 0; j < n; ++j) {
+        const uint32_t in = (a.g0 >> j) & (uint32_t)u;
+        o0 |= ((in ^ (uint32_t)__builtin_popcount(a.gs[j] & (uint32_t)ps0[i])) & 1u) << j;
+        o1 |= ((in ^ (uint32_t)__builtin_popcount(a.gs[j] & (uint32_t)ps1[i])) & 1u) << j;
+      }
+      bm0[i] = bm1[i] = 0u;
+#pragma unroll
+      for (uint32_t y = 0; y < (1u << n); ++y) {
+        bm0[i] |= (uint32_t)__builtin_popcount(o0 ^ y) << (2 * y);
+        bm1[i] |= (uint32_t)__builtin_popcount(o1 ^ y) << (2 * y);
+      }
+    }
+  }
+
+  // D -= min D over the states; returns the min
+  __device__ __forceinline__ int normalise(int (&D)[SPL]) const {
+    int mn = D[0];
+#pragma unroll
+    for (int i = 1; i < SPL; ++i) mn = min(mn, D[i]);
+#pragma unroll
+    for (int k = 1; k < kWave; k <<= 1) mn = min(mn, __shfl_xor(mn, k));
+#pragma unroll
+    for (int i = 0; i < SPL; ++i) D[i] -= mn;
+    return mn;
+  }
+
+  __device__ __forceinline__ void store(uint8_t* vec, const int (&D)[SPL]) const {
+    if (lane < S) {
+#pragma unroll
+      for (int i = 0; i < SPL; ++i) vec[state(i)] = (uint8_t)D[i];
+    }
+  }
+
+  __device__ __forceinline__ void load(const uint8_t* vec, int (&D)[SPL]) const {
+#pragma unroll
+    for (int i = 0; i < SPL; ++i) D[i] = vec[state(i)];
+  }
+
+  // steps [t0, t1) of Eq. 4-5 on D (not normalised); record: the decision words to
+  // dec[(t - t0) SPL + i]: lane j keeps the ballot of a 64-step chunk's step j, and after the
+  // chunk the wave stores its 64 words as one contiguous piece (a slot per step in LDS instead,
+  // one ds_write_b64 per step, made the loop LDS-bound: the two ds_bpermute already take two
+  // thirds of the LDS pipe's time).  LDS: st kStageDw dwords, met 2 S ints (S > 64).
+  template <bool record>
+  __device__ __forceinline__ void run(const VArgs& a, int64_t t0, int64_t t1, int (&D)[SPL], uint64_t* dec,
+                                      uint32_t* st, int* met) const {
+    constexpr uint32_t ymask = (1u << n) - 1u;
+    uint32_t mlo[SPL], mhi[SPL];                         // lane j: the decision word of the chunk's step j
+#pragma unroll
+    for (int i = 0; i < SPL; ++i) mlo[i] = mhi[i] = 0u;
+    int cur = 0;
+    for (int64_t seg = t0; seg < t1; seg += kSeg) {
+      const int cnt = (int)min((int64_t)kSeg, t1 - seg);
+      __syncthreads();                                   // the previous segment has been read
+      stage_bits<n>(a, seg, cnt, st, lane);
+      __syncthreads();
+      uint32_t q = (uint32_t)((a.start + (int64_t)n * seg) & 31);
+      int dw = -1;                                       // the staged dwords dw, dw + 1 in SGPRs: y_t is scalar work
+      uint32_t wlo = 0u, whi = 0u;
+      for (int j0 = 0; j0 < cnt; j0 += kWave) {
+        const int c64 = min(kWave, cnt - j0);
+        for (int jj = 0; jj < c64; ++jj, q += n) {
+          if ((int)(q >> 5) != dw) {
+            dw = (int)(q >> 5);
+            wlo = (uint32_t)__builtin_amdgcn_readfirstlane((int)st[dw]);
+            whi = (uint32_t)__builtin_amdgcn_readfirstlane((int)st[dw + 1]);
+          }
+          const uint32_t y2 = 2u * ((uint32_t)((((uint64_t)whi << 32) | wlo) >> (q & 31u)) & ymask);
+          if constexpr (SPL > 1) {
+#pragma unroll
+            for (int i = 0; i < SPL; ++i) met[cur * S + state(i)] = D[i];
+            __syncthreads();
+          }
+#pragma unroll
+          for (int i = 0; i < SPL; ++i) {
+            int a0, a1;
+            if constexpr (SPL > 1) {
+              a0 = met[cur * S + ps0[i]];
+              a1 = met[cur * S + ps1[i]];
+            } else {
+              a0 = __shfl(D[0], ps0[0]);
+              a1 = __shfl(D[0], ps1[0]);
+            }
+            const int c0 = a0 + (int)((bm0[i] >> y2) & 3u), c1 = a1 + (int)((bm1[i] >> y2) & 3u);
+            bool d = c1 < c0;                            // ties keep b = 0
+            D[i] = min(c0, c1);
+            if constexpr (record) {
+              if constexpr (S < kWave) d = d && lane < S;
+              const uint64_t bal = __builtin_amdgcn_ballot_w64(d);
+              if (lane == jj) {
+                mlo[i] = (uint32_t)bal;
+                mhi[i] = (uint32_t)(bal >> 32);
+              }
+            }
+          }
+          cur ^= 1;
+        }
+        if constexpr (record) {
+          if (lane < c64) {
+            uint64_t* p = dec + ((seg - t0) + j0 + lane) * SPL;
+#pragma unroll
+            for (int i = 0; i < SPL; ++i) p[i] = ((uint64_t)mhi[i] << 32) | mlo[i];
+          }
+        }
+      }
+    }
+  }
+};
+
+template <int m, int n>
+__global__ __launch_bounds__(kWave) void viterbi_forward_kernel(VArgs a) {
+  using Sh = Shape<m>;
+  __shared__ uint32_t st[kStageDw];
+  __shared__ int met[Sh::SPL > 1 ? 2 * Sh::S : 1];
+  Lane<m, n> ln;
+  ln.init(a);
+  const int64_t b = blockIdx.x;
+  const int64_t lo = b * a.L, hi = min(a.T, lo + a.L), t0 = max((int64_t)0, lo - a.W);
+  int D[Sh::SPL];
+#pragma unroll
+  for (int i = 0; i < Sh::SPL; ++i) D[i] = 0;
+  if (t0 < lo) {
+    ln.template run<false>(a, t0, lo, D, nullptr, st, met);
+    ln.normalise(D);
+  }
+  ln.store(a.warm + b * Sh::S, D);
+  ln.template run<true>(a, lo, hi, D, a.dec + lo * Sh::SPL, st, met);
+  const int mn = ln.normalise(D);
+  ln.store(a.endv + b * Sh::S, D);
+  if (ln.lane == 0) a.norm[b] = mn;
+}
+
+__global__ void viterbi_compare_kernel(VArgs a, int S) {
+  const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= a.nb) return;
+  int diff = 0;
+  if (b > 0) {
+    const uint8_t* w = a.warm + b * S;
+    const uint8_t* e = a.endv + (b - 1) * S;
+    for (int s = 0; s < S; ++s) diff |= w[s] != e[s];
+  }
+  a.mis[b] = diff;
+}
+
+template <int m, int n>
+__global__ __launch_bounds__(kWave) void viterbi_join_kernel(VArgs a) {
+  using Sh = Shape<m>;
+  __shared__ uint32_t st[kStageDw];
+  __shared__ int met[Sh::SPL > 1 ? 2 * Sh::S : 1];
+  Lane<m, n> ln;
+  ln.init(a);
+  int D[Sh::SPL];
+  unsigned long long reruns = 0;
+  int64_t b = 1;
+  while (b < a.nb) {
+    const int64_t idx = b + ln.lane;
+    const uint64_t bal = __ballot(idx < a.nb && a.mis[idx] != 0);
+    if (!bal) { b += kWave; continue; }
+    b += __builtin_ctzll(bal);
+    ln.load(a.endv + (b - 1) * Sh::S, D);                // block b - 1 stands: its end vector is the true one
+    while (b < a.nb) {
+      bool diff = false;
+#pragma unroll
+      for (int i = 0; i < Sh::SPL; ++i) diff |= D[i] != (int)a.warm[b * Sh::S + ln.state(i)];
+      if (!__any(diff)) break;
+      ++reruns;
+      const int64_t lo = b * a.L, hi = min(a.T, lo + a.L);
+      ln.template run<true>(a, lo, hi, D, a.dec + lo * Sh::SPL, st, met);
+      const int mn = ln.normalise(D);
+      ln.store(a.endv + b * Sh::S, D);
+      if (ln.lane == 0) a.norm[b] = mn;
+      ++b;
+    }
+    ++b;                                                 // block b joined: scan on behind it
+  }
+  if (ln.lane == 0) a.cnt[1] = reruns;
+}
+
+__device__ __forceinline__ uint64_t readlane64(uint64_t v, int j) {
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, j);
+  const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), j);
+  return ((uint64_t)hi << 32) | lo;
+}
+
+// survivor of state s at step hi followed back to step lo (s may differ from lane to lane);
+// write (s wave-uniform, lo a multiple of 32): the input bits of steps [lo, hi) to d_bits
+template <int m, bool write>
+__device__ __forceinline__ int trace_range(const VArgs& a, int64_t lo, int64_t hi, int s, int lane) {
+  constexpr int SPL = Shape<m>::SPL;
+  // the block's own chain is wave-uniform: in SGPRs it runs on the scalar unit, whose
+  // dependent shift / and / or chain per step is several times shorter than the vector one
+  if constexpr (write) s = __builtin_amdgcn_readfirstlane(s);
+  const int nch = (int)((hi - lo + 63) >> 6);
+  uint64_t w[SPL], wn[SPL];                  // this chunk's words, and the next one's on their way
+#pragma unroll
+  for (int i = 0; i < SPL; ++i) {
+    wn[i] = 0ull;
+    if (nch > 0 && lo + 64 * (int64_t)(nch - 1) + lane < hi) wn[i] = a.dec[(lo + 64 * (int64_t)(nch - 1) + lane) * SPL + i];
+  }
+  for (int c = nch - 1; c >= 0; --c) {
+    const int64_t base = lo + 64 * (int64_t)c;
+    const int cnt = (int)min((int64_t)64, hi - base);
+#pragma unroll
+    for (int i = 0; i < SPL; ++i) {
+      w[i] = wn[i];
+      if (c > 0) wn[i] = a.dec[(base - 64 + lane) * SPL + i];   // a whole chunk: below the last one
+    }
+    uint64_t out = 0ull;
+    for (int j = cnt - 1; j >= 0; --j) {
+      uint64_t x = readlane64(w[0], j);
+#pragma unroll
+      for (int i = 1; i < SPL; ++i) {
+        const uint64_t xi = readlane64(w[i], j);
+        if ((s >> 6) == i) x = xi;
+      }
+      const int d = (int)((x >> (s & 63)) & 1ull);
+      if constexpr (write) out |= (uint64_t)(s & 1) << j;
+      s = (s >> 1) | (d << (m - 1));
+    }
+    if constexpr (write) {
+      if (lane == 0) {
+        a.bits[base >> 5] = (uint32_t)out;
+        if (base + 32 < hi) a.bits[(base >> 5) + 1] = (uint32_t)(out >> 32);
+      }
+    }
+  }
+  return s;
+}
+
+// lowest-index state with D_T = 0
+template <int m>
+__device__ __forceinline__ int end_state(const VArgs& a, int lane) {
+  constexpr int S = Shape<m>::S, SPL = Shape<m>::SPL;
+  int sT = 0;
+#pragma unroll
+  for (int i = SPL - 1; i >= 0; --i) {
+    const uint64_t bal = __ballot(lane < S && a.endv[(a.nb - 1) * S + (lane & (S - 1)) + kWave * i] == 0);
+    if (bal) sT = kWave * i + __builtin_ctzll(bal);
+  }
+  return sT;
+}
+
+template <int m>
+__global__ __launch_bounds__(kWave) void viterbi_look_kernel(VArgs a) {
+  constexpr int S = Shape<m>::S, SPL = Shape<m>::SPL;
+  const int lane = threadIdx.x;
+  const int64_t b = blockIdx.x;
+  const int64_t lo = b * a.L, hi = min(a.T, lo + a.L), e = min(a.T, lo + a.L + a.D);
+  int x;
+  bool cert = true;
+  if (e == a.T) {
+    x = trace_range<m, false>(a, hi, a.T, end_state<m>(a, lane), lane);
+  } else {
+    x = 0;
+#pragma unroll
+    for (int i = 0; i < SPL; ++i) {
+      const int r = trace_range<m, false>(a, hi, e, (lane & (S - 1)) + kWave * i, lane);
+      if (i == 0) x = __builtin_amdgcn_readfirstlane(r);
+      cert = cert && __all(r == x);
+    }
+  }
+  if (lane == 0) {
+    a.xs[b] = x;
+    a.unc[b] = cert ? 0 : 1;
+    if (!cert) atomicAdd(&a.cnt[2], 1ull);
+    atomicAdd(&a.cnt[0], (unsigned long long)a.norm[b]);
+  }
+}
+
+// The certified blocks' own chains, lane = block: 64 independent chains per wave instead of
+// one chain computed 64 times over.  A lane's decision words are contiguous; it reads them a
+// 128-byte line (16 / SPL steps) at a time, the line below already on its way.  The steps of
+// the last block at or past T are skipped (their words are allocated, never written).
+template <int m>
+__global__ __launch_bounds__(kWave) void viterbi_trace_kernel(VArgs a) {
+  constexpr int SPL = Shape<m>::SPL, K = 16 / SPL;
+  const int64_t b = (int64_t)blockIdx.x * kWave + threadIdx.x;
+  if (b >= a.nb || a.unc[b] != 0) return;
+  const int64_t lo = b * a.L;
+  const int len = (int)(min(a.T, lo + a.L) - lo);
+  const uint64_t* d = a.dec + lo * SPL;
+  uint32_t* bits = a.bits + (lo >> 5);
+  int s = a.xs[b];
+  uint64_t w[16], wn[16];
+  const int nsub = a.L / K;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) wn[i] = d[(int64_t)(nsub - 1) * 16 + i];
+  uint32_t out = 0u;
+  for (int c = nsub - 1; c >= 0; --c) {
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      w[i] = wn[i];
+      if (c > 0) wn[i] = d[(int64_t)(c - 1) * 16 + i];
+    }
+#pragma unroll
+    for (int k = K - 1; k >= 0; --k) {
+      const int t = c * K + k;
+      uint64_t x = w[k * SPL];
+#pragma unroll
+      for (int i = 1; i < SPL; ++i)
+        if ((s >> 6) == i) x = w[k * SPL + i];
+      const int dd = (int)((x >> (s & 63)) & 1ull);
+      if (t < len) {
+        out |= (uint32_t)(s & 1) << (t & 31);
+        s = (s >> 1) | (dd << (m - 1));
+      }
+    }
+    if (((c * K) & 31) == 0) {                           // steps [cK, cK + 32) are done: one output word
+      if (c * K < len) bits[(c * K) >> 5] = out;
+      out = 0u;
+    }
+  }
+  a.sst[b] = s;
+}
+
+template <int m>
+__global__ __launch_bounds__(kWave) void viterbi_fix_kernel(VArgs a) {
+  const int lane = threadIdx.x;
+  int64_t carry_b = -1;
+  int carry_s = 0;
+  for (int64_t top = a.nb; top > 0; top -= kWave) {
+    const int64_t idx = top - 1 - lane;                  // lane k: block top - 1 - k, so ctz is the highest block
+    uint64_t bal = __ballot(idx >= 0 && a.unc[idx] != 0);
+    while (bal) {
+      const int64_t b = top - 1 - __builtin_ctzll(bal);
+      bal &= bal - 1;
+      // the last block is always certified, so b + 1 < nb; an uncertified b + 1 was fixed just now
+      const int x = carry_b == b + 1 ? carry_s : a.sst[b + 1];
+      const int s0 = trace_range<m, true>(a, b * a.L, min(a.T, (b + 1) * a.L), x, lane);
+      if (lane == 0) a.sst[b] = s0;
+      carry_b = b;
+      carry_s = s0;
+    }
+  }
+  const int sT = end_state<m>(a, lane);
+  if (lane == 0) {
+    a.stats[0] = (int64_t)a.cnt[0];
+    a.stats[1] = a.nb;
+    a.stats[2] = (int64_t)a.cnt[1];
+    a.stats[3] = (int64_t)a.cnt[2];
+    a.stats[4] = carry_b == 0 ? carry_s : a.sst[0];
+    a.stats[5] = sT;
+    a.stats[6] = a.L;
+    a.stats[7] = a.W;
+    a.stats[8] = a.D;
+  }
+}
+
+#define HIP_CHECK(x)                                                                      \
+  do {                                                                                    \
+    hipError_t e_ = (x);                                                                  \
+    if (e_ != hipSuccess) {                                                               \
+      cvd::set_error(std::string("HIP error '") + hipGetErrorString(e_) + "' at " #x);     \
+      return CVD_E_HIP;                                                                   \
+    }                                                                                     \
+  } while (0)
+
+int invalid(const char* what) {
+  cvd::set_error(std::string("viterbi_decode: ") + what);
+  return CVD_E_INVALID;
+}
+
+int unsupported(const char* what) {
+  cvd::set_error(std::string("viterbi_decode: ") + what);
+  return CVD_E_UNSUPPORTED;
+}
+
+int64_t round16(int64_t x) { return (x + 15) / 16 * 16; }
+
+struct Layout {
+  int64_t nb, dec, warm, endv, norm, sst, xs, mis, unc, cnt, total;
+};
+
+// T in 1..2^31 - 1, L >= 32: nb L < 2^32, every size far below 2^63
+Layout layout_of(int m, int64_t T, int64_t L) {
+  const int64_t S = (int64_t)1 << m, spl = S > kWave ? S / kWave : 1;
+  Layout y{};
+  y.nb = (T + L - 1) / L;
+  int64_t off = 0;
+  y.dec = off;  off += round16(y.nb * L * spl * 8);
+  y.warm = off; off += round16(y.nb * S);
+  y.endv = off; off += round16(y.nb * S);
+  y.norm = off; off += round16(y.nb * 4);
+  y.sst = off;  off += round16(y.nb * 4);
+  y.xs = off;   off += round16(y.nb * 4);
+  y.mis = off;  off += round16(y.nb * 4);
+  y.unc = off;  off += round16(y.nb * 4);
+  y.cnt = off;  off += 64;
+  y.total = off;
+  return y;
+}
+
+// 0 if block is acceptable (resolving 0 to the default), else the error
+int resolve_block(int32_t block, int32_t* L) {
+  if (block == 0) block = CVD_VITERBI_BLOCK;
+  if (block < 32 || block % 32) return invalid("block must be 0 (default) or a multiple of 32, at least 32");
+  *L = block;
+  return CVD_OK;
+}
+
+template <int n>
+int launch_all(int m, const VArgs& a, hipStream_t st) {
+  using K = void (*)(VArgs);
+#define CVD_V_ROW(KERN) {KERN<1, n>, KERN<2, n>, KERN<3, n>, KERN<4, n>, KERN<5, n>, KERN<6, n>, KERN<7, n>, KERN<8, n>}
+  static const K fwd[8] = CVD_V_ROW(viterbi_forward_kernel);
+  static const K join[8] = CVD_V_ROW(viterbi_join_kernel);
+#undef CVD_V_ROW
+  static const K look[8] = {viterbi_look_kernel<1>, viterbi_look_kernel<2>, viterbi_look_kernel<3>,
+                            viterbi_look_kernel<4>, viterbi_look_kernel<5>, viterbi_look_kernel<6>,
+                            viterbi_look_kernel<7>, viterbi_look_kernel<8>};
+  static const K trace[8] = {viterbi_trace_kernel<1>, viterbi_trace_kernel<2>, viterbi_trace_kernel<3>,
+                             viterbi_trace_kernel<4>, viterbi_trace_kernel<5>, viterbi_trace_kernel<6>,
+                             viterbi_trace_kernel<7>, viterbi_trace_kernel<8>};
+  static const K fix[8] = {viterbi_fix_kernel<1>, viterbi_fix_kernel<2>, viterbi_fix_kernel<3>, viterbi_fix_kernel<4>,
+                           viterbi_fix_kernel<5>, viterbi_fix_kernel<6>, viterbi_fix_kernel<7>, viterbi_fix_kernel<8>};
+  HIP_CHECK(hipMemsetAsync(a.cnt, 0, 64, st));
+  hipLaunchKernelGGL(fwd[m - 1], dim3((unsigned)a.nb), dim3(kWave), 0, st, a);
+  HIP_CHECK(hipGetLastError());
+  if (a.nb > 1) {
+    hipLaunchKernelGGL(viterbi_compare_kernel, dim3((unsigned)((a.nb + 255) / 256)), dim3(256), 0, st, a, 1 << m);
+    HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(join[m - 1], dim3(1), dim3(kWave), 0, st, a);
+    HIP_CHECK(hipGetLastError());
+  }
+  hipLaunchKernelGGL(look[m - 1], dim3((unsigned)a.nb), dim3(kWave), 0, st, a);
+  HIP_CHECK(hipGetLastError());
+  hipLaunchKernelGGL(trace[m - 1], dim3((unsigned)((a.nb + kWave - 1) / kWave)), dim3(kWave), 0, st, a);
+  HIP_CHECK(hipGetLastError());
+  hipLaunchKernelGGL(fix[m - 1], dim3(1), dim3(kWave), 0, st, a);
+  HIP_CHECK(hipGetLastError());
+  return CVD_OK;
+}
+
+}  // namespace
+
+extern "C" int64_t cvd_viterbi_workspace_bytes(int32_t n, int32_t m, int64_t T, int32_t block) {
+  if (n < 2 || n > 3 || m < 1 || m > 8) return invalid("needs n in 2..3 and m in 1..8");
+  if (T < 0 || T > INT32_MAX) return invalid("T must be 0..2^31 - 1");
+  int32_t L;
+  if (resolve_block(block, &L)) return CVD_E_INVALID;
+  return layout_of(m, std::max<int64_t>(T, 1), L).total;
+}
+
+extern "C" int cvd_viterbi_decode(const cvd_code* code, const void* d_capture, int64_t nbits, int32_t format,
+                                  int64_t start, int64_t T, int32_t block, int32_t warm, int32_t depth,
+                                  uint32_t* d_bits, int64_t* d_stats, void* d_work, void* stream) {
+  if (!code || !code->taps) return invalid("null code");
+  if (code->k != 1 || code->n < 2 || code->n > 3 || code->m < 1 || code->m > 8)
+    return unsupported("needs k = 1, n in 2..3 and m in 1..8");
+  const int n = code->n, m = code->m;
+  if (format != CVD_CAPTURE_LSB && format != CVD_CAPTURE_MSB && format != CVD_CAPTURE_BYTES)
+    return invalid("unknown capture format");
+  if (T < 0 || T > INT32_MAX) return invalid("T must be 0..2^31 - 1");
+  if (start < 0 || nbits < 0) return invalid("needs start, nbits >= 0");
+  int64_t end;
+  if (__builtin_mul_overflow(T, (int64_t)n, &end) || __builtin_add_overflow(end, start, &end))
+    return invalid("start + n * T overflows int64");
+  if (end > nbits) return invalid("the symbols do not lie inside [0, nbits)");
+  int32_t L;
+  if (resolve_block(block, &L)) return CVD_E_INVALID;
+  if (warm < -1) return invalid("warm must be >= 0, or -1 (default)");
+  if (depth < -1) return invalid("depth must be >= 0, or -1 (default)");
+  const int32_t W = warm < 0 ? CVD_VITERBI_WARM(m) : warm, D = depth < 0 ? CVD_VITERBI_DEPTH(m) : depth;
+  if (T == 0) return CVD_OK;
+  if (!d_capture || !d_bits || !d_stats || !d_work || ((uintptr_t)d_capture & 15) || ((uintptr_t)d_work & 15) ||
+      ((uintptr_t)d_bits & 3) || ((uintptr_t)d_stats & 7))
+    return invalid("d_capture, d_work (16-byte aligned), d_bits (4-byte) and d_stats (8-byte) must be non-null");
+
+  const Layout y = layout_of(m, T, L);
+  VArgs a{};
+  a.cap = static_cast<const uint4*>(d_capture);
+  const int64_t nbytes = format == CVD_CAPTURE_BYTES ? nbits : nbits / 8 + (nbits % 8 != 0);
+  a.nu4 = nbytes / 16 + (nbytes % 16 != 0);
+  a.format = format; a.start = start; a.T = T; a.L = L; a.W = W; a.D = D; a.nb = y.nb;
+  for (int j = 0; j < n; ++j) {
+    const uint8_t* t = code->taps + (size_t)j * (m + 1);
+    if (t[0] & 1) a.g0 |= 1u << j;
+    for (int d = 1; d <= m; ++d)
+      if (t[d] & 1) a.gs[j] |= 1u << (d - 1);
+  }
+  char* w = static_cast<char*>(d_work);
+  a.dec = reinterpret_cast<uint64_t*>(w + y.dec);
+  a.warm = reinterpret_cast<uint8_t*>(w + y.warm);
+  a.endv = reinterpret_cast<uint8_t*>(w + y.endv);
+  a.norm = reinterpret_cast<int32_t*>(w + y.norm);
+  a.sst = reinterpret_cast<int32_t*>(w + y.sst);
+  a.xs = reinterpret_cast<int32_t*>(w + y.xs);
+  a.mis = reinterpret_cast<int32_t*>(w + y.mis);
+  a.unc = reinterpret_cast<int32_t*>(w + y.unc);
+  a.cnt = reinterpret_cast<unsigned long long*>(w + y.cnt);
+  a.bits = d_bits;
+  a.stats = d_stats;
+  hipStream_t st = (hipStream_t)stream;
+  return n == 2 ? launch_all<2>(m, a, st) : launch_all<3>(m, a, st);
+}

@@ -23,6 +23,8 @@
  *                             (a captured serial bitstream cut into windows in cvd_generate's layout)
  *   (none: the reference's templates come from known generators)                   cvd_parity_sweep
  *                             (all 2^B parity templates of a capture at once: histogram + WHT)
+ *   (none: the reference keeps no survivor decisions, viterbi_markov.py:139-159)   cvd_viterbi_decode
+ *                             (hard-decision Viterbi decoder of a capture: bits, error count, end states)
  *   alpha_exponent.py:83-156  learn_transition_tensor (joint counts)              cvd_count_transitions
  *   alpha_exponent.py:159-188 compute_error_exponent: M(u) for a u grid           cvd_chernoff_build(_dense)
  *   alpha_exponent.py:69-76   spectral_radius (Perron root of M(u) >= 0)           cvd_spectral_radius
@@ -418,6 +420,65 @@ int64_t cvd_parity_sweep_workspace_bytes(int32_t n, int32_t span, int32_t n_phas
 int cvd_parity_sweep(const void* d_capture, int64_t nbits, int32_t format, int32_t n, int32_t span,
                      int64_t start, int64_t T, int32_t n_phase, int64_t* d_sat, void* d_work,
                      void* stream);
+
+/* ---- hard-decision Viterbi decoder of a capture (nothing in the reference) ----
+ * What was sent?  The Eq. 4-5 recursion (cvd_metric_step) with its survivor decisions kept:
+ * the information bits of the maximum-likelihood path, its Hamming distance to the capture
+ * (errors / (n*T) estimates the channel's crossover probability, the p that scan needs) and
+ * its end states.  Exact: the result is the sequential decoder's stated here, bit for bit,
+ * and does not depend on block, warm, depth or the launch shape.
+ *
+ * Code shapes: k = 1, n in {2, 3}, 1 <= m <= 8; anything else CVD_E_UNSUPPORTED.
+ * Capture: read exactly as cvd_pack_windows reads it (CVD_CAPTURE_*, the same 16-byte
+ * alignment and readability rule, 64-bit bit positions); capture bit start + n*t + j is
+ * output j of step t, 0 <= t < T; y_t is the received n-bit word of step t.
+ * States and branches (viterbi_markov.py:60-106): bit 0 of a state is the most recent input;
+ * the branch from state s with input u goes to ((s << 1) | u) & (2^m - 1), and its output j is
+ * taps[j][0][0]*u ^ sum_{d>=1} taps[j][0][d]*bit_{d-1}(s).
+ * Forward (Eq. 4-5 with the decisions recorded): D_0(s) = 0 for every s.  For step t and
+ * next state s', u = s' & 1 and ps_b = (s' >> 1) | (b << (m-1)), b in {0, 1}:
+ *   D'(s') = min_b [D_t(ps_b) + d_H(out(ps_b, u), y_t)],
+ *   dec_t(s') = 1 iff b = 1 is strictly smaller (ties keep b = 0: the reference's
+ *   `val < best` in trellis order, viterbi_markov.py:150-156),
+ *   D_{t+1} = D' - min D'.                       (relative metrics fit a byte: D <= n*m <= 24)
+ * End and traceback: s_T is the lowest-index state with D_T = 0; for t = T-1 ... 0:
+ *   u_t = s_{t+1} & 1,  s_t = (s_{t+1} >> 1) | (dec_t(s_{t+1}) << (m-1));
+ *   errors = sum_t d_H(out(s_t, u_t), y_t).
+ *
+ * d_bits: ceil(T/32) words, bit t = u_t LSB first (as bytes on this little-endian target a
+ * CVD_CAPTURE_LSB capture of T bits: it can go back into cvd_parity_sweep, e.g. for an outer
+ * code); the bits of the last word at or past T are zero.  4-byte aligned.
+ * d_stats: int64[9], written (not accumulated), 8-byte aligned:
+ *   [0] errors  [1] number of blocks  [2] forward reruns  [3] traceback fix-ups
+ *   [4] s_0  [5] s_T  [6] resolved block  [7] resolved warm  [8] resolved depth
+ * block = L: a multiple of 32, at least 32 (a block owns whole output words); 0 = default.
+ * warm = W >= 0, depth = D >= 0; -1 = default.  Defaults (measured): */
+#define CVD_VITERBI_BLOCK 4096
+#define CVD_VITERBI_WARM(m) (64 * (m))
+#define CVD_VITERBI_DEPTH(m) (24 * ((m) + 2))
+/* The counters are part of the contract (a test can prove which path ran):
+ *   block b covers steps [b*L, min(T, (b+1)*L)); its warm vector is the relative metric
+ *   vector at step b*L of a recursion started from all zeros at step max(0, b*L - W);
+ *   stats[2] = #{b >= 1 : warm vector != the true D_{b*L}} (each such block is run again
+ *   from the true vector);
+ *   with e_b = min(T, (b+1)*L + D): if e_b = T block b traces from the true s_T and is
+ *   certified; otherwise it is certified iff the survivors of all 2^m states at step e_b
+ *   (true decisions) pass through one single state at step (b+1)*L;
+ *   stats[3] = #{uncertified blocks} (each traced again, in descending order, from the start
+ *   state of the block after it).
+ * d_work: cvd_viterbi_workspace_bytes(n, m, T, block) bytes, 16-byte aligned: per step
+ * max(8, 2^m / 8) bytes of decision words (blocks rounded up to L steps), per block two
+ * metric vectors and a few words (< 0 with the error set for n, m outside the shapes above,
+ * T < 0 or > 2^31 - 1, or a bad block).  Asynchronous on `stream`.
+ * CVD_E_INVALID, before the device is touched, cvd_last_error() naming viterbi_decode, for:
+ * an unknown format; start < 0, nbits < 0, T < 0 or T > 2^31 - 1; start + n*T > nbits or an
+ * int64 overflow in it; a bad block, warm or depth; null or misaligned pointers when T > 0
+ * (d_capture, d_work 16-byte, d_bits 4-byte, d_stats 8-byte aligned).  T == 0: CVD_OK
+ * without a launch (nothing is written).  Kernels: csrc/cvd_decode.hip. */
+int64_t cvd_viterbi_workspace_bytes(int32_t n, int32_t m, int64_t T, int32_t block);
+int cvd_viterbi_decode(const cvd_code* code, const void* d_capture, int64_t nbits, int32_t format,
+                       int64_t start, int64_t T, int32_t block, int32_t warm, int32_t depth,
+                       uint32_t* d_bits, int64_t* d_stats, void* d_work, void* stream);
 
 /* ---- error-exponent engine (alpha_exponent.py, Eq. 7) ---------------------
  * Joint counts of (metric state i, received word r) along received streams
