@@ -19,8 +19,13 @@
 //   spectral_radius_kernel    rho(M(u)) for a batch of u, one workgroup each: power
 //                             iteration on the positive matrix with Collatz-
 //                             Wielandt bounds  min_i (Mx)_i/x_i <= rho <= max_i (Mx)_i/x_i
-//                             until they agree to `tol` (Perron-Frobenius: M > 0)
-//   rho_*_kernel              the same iteration for K above the LDS limit (the
+//                             until they agree to `tol` (Perron-Frobenius: M > 0).
+//                             The estimate is certified only when the bounds are
+//                             finite and meet; otherwise (periodic, reducible or
+//                             defective M) it is the plain norm ratio and the
+//                             caller must not trust it (exponent.py falls back)
+//   rho_*_kernel              the same iteration for K above the LDS limit of
+//                             K = 10,232 (2 K doubles + 128 B in 160 KiB; the
 //                             m = 4 rate-1/2 automata, K = 150,743): vectors in
 //                             HBM, every u at once, one launch per phase
 //   count_transitions_global_kernel  the joint counts for S >= 4096 (records read
@@ -230,11 +235,17 @@ __global__ __launch_bounds__(kRhoBlock) void spectral_radius_kernel(RhoArgs p) {
   for (int i = threadIdx.x; i < K; i += kRhoBlock) x[i] = 1.0;
   __syncthreads();
   // x > 0 with max x = 1: for any nonnegative M, min_i (Mx)_i/x_i <= rho <=
-  // max_i (Mx)_i/x_i; the bounds meet for irreducible M (every M(u) of Eq. 7
-  // is positive).  A reducible M (dense input) can keep them apart: then the
-  // estimate is max_i (Mx)_i, the power-iteration norm ratio, once it is
-  // stable to tol / 100 between iterations.
-  double lo = 0.0, hi = 0.0, sx = (double)K, est = 0.0, prev = -1.0;
+  // max_i (Mx)_i/x_i; the bounds meet for irreducible aperiodic M (every M(u)
+  // of Eq. 7 is positive).  The upper bound needs every x_i > 0: a row with
+  // x_i = 0 counts as +inf there (0/0 would drop out of fmax as a NaN), and a
+  // bracket is met only when both bounds are finite.  A periodic or reducible
+  // M (dense input) keeps them apart: then the estimate is max_i (Mx)_i, the
+  // power-iteration norm ratio, once it is stable to tol / 100 between
+  // iterations and the bracket has stopped shrinking, or after max_iter --
+  // uncertified, and wrong for some such M.  (The norm ratio alone is no
+  // stopping test: on its way to the limit it can pass through an extremum,
+  // stable for one iteration while the bracket is still 50 tol wide.)
+  double lo = 0.0, hi = 0.0, sx = (double)K, est = 0.0, prev = -1.0, pgap = INFINITY;
   bool met = false;
   int it = 0;
   for (; it < p.max_iter; ++it) {
@@ -249,18 +260,25 @@ __global__ __launch_bounds__(kRhoBlock) void spectral_radius_kernel(RhoArgs p) {
         for (int e = 0; e < E; ++e) s += row[e] * x[e];
       }
       y[i] = s;
-      const double ratio = s / x[i];
-      rmin = fmin(rmin, ratio);
-      rmax = fmax(rmax, ratio);
+      const double xi = x[i];
+      if (xi > 0.0) {
+        const double ratio = s / xi;
+        rmin = fmin(rmin, ratio);
+        rmax = fmax(rmax, ratio);
+      } else {
+        rmax = INFINITY;
+      }
       ymax = fmax(ymax, s);
     }
     lo = block_reduce(rmin, s_red, 1);
     hi = block_reduce(rmax, s_red, 2);
     ymax = block_reduce(ymax, s_red, 2);
     est = ymax;   // ||M x||_inf with ||x||_inf = 1
-    if (hi - lo <= p.tol * hi) { met = true; ++it; break; }
-    if (!(ymax > 0.0) || fabs(est - prev) <= 0.01 * p.tol * est) { ++it; break; }
+    if (isfinite(lo) && isfinite(hi) && hi - lo <= p.tol * hi) { met = true; ++it; break; }
+    const double gap = hi - lo;
+    if (!(ymax > 0.0) || (fabs(est - prev) <= 0.01 * p.tol * est && !(gap < pgap))) { ++it; break; }
     prev = est;
+    pgap = gap;
     double sl = 0.0;
     for (int i = threadIdx.x; i < K; i += kRhoBlock) {
       const double v = y[i] / ymax;
@@ -313,7 +331,9 @@ __global__ __launch_bounds__(kGBlock) void rho_matvec_kernel(GRhoArgs g) {
     const int32_t* cr = g.cols + (int64_t)i * g.E;
     for (int e = 0; e < g.E; ++e) s += row[e] * xu[cr[e]];
     g.y[ui] = s;
-    rmin = rmax = s / xu[i];
+    const double xi = xu[i];
+    if (xi > 0.0) rmin = rmax = s / xi;
+    else rmax = INFINITY;   // no upper bound from a row with x_i = 0 (see spectral_radius_kernel)
     ym = s;
   }
   rmin = block_reduce(rmin, s_red, 1);
@@ -339,10 +359,11 @@ __global__ __launch_bounds__(kGBlock) void rho_step_kernel(GRhoArgs g) {
   hi = block_reduce(hi, s_red, 2);
   ym = block_reduce(ym, s_red, 2);
   if (threadIdx.x == 0) {
+    const double pgap = st[7] > 0.0 ? st[4] - st[3] : INFINITY;   // the previous iteration's bracket
     st[3] = lo; st[4] = hi; st[1] = ym; st[5] = ym;
     st[7] += 1.0;
-    if (hi - lo <= g.tol * hi) st[6] = 1.0;
-    else if (!(ym > 0.0) || fabs(ym - st[2]) <= 0.01 * g.tol * ym) st[6] = 2.0;
+    if (isfinite(lo) && isfinite(hi) && hi - lo <= g.tol * hi) st[6] = 1.0;
+    else if (!(ym > 0.0) || (fabs(ym - st[2]) <= 0.01 * g.tol * ym && !(hi - lo < pgap))) st[6] = 2.0;
     else st[2] = ym;
   }
 }
@@ -515,7 +536,7 @@ extern "C" int cvd_spectral_radius(int32_t K, int32_t E, const double* d_a, cons
   const size_t lds = (size_t)2 * K * sizeof(double) + 16 * sizeof(double);
   const char* force = std::getenv("CVD_RHO_GLOBAL");   // tests: the HBM path at small K
   if (lds > 160 * 1024 || (force && force[0] == '1')) {
-    if (!d_cols) { cvd::set_error("spectral_radius: K > 10000 needs the structured (cols) form"); return CVD_E_UNSUPPORTED; }
+    if (!d_cols) { cvd::set_error("spectral_radius: K > 10232 needs the structured (cols) form"); return CVD_E_UNSUPPORTED; }
     if (U == 0) return CVD_OK;
     return spectral_radius_global(K, E, d_a, d_vals, d_cols, U, tol, max_iter, d_rho, d_iters, (hipStream_t)stream);
   }

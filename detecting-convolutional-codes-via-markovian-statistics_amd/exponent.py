@@ -28,7 +28,10 @@ chain is the detector's own: encoder and BSC(p) of the trial spec (D1/D2),
 metric states of the decoder's BFS automaton, `chains` independent chains of
 burn_in + length/chains steps (chains = 1: one chain, as the reference).
 rho is the Perron root (the spectral radius of the nonnegative M(u)); the
-reference computes it with np.linalg.eigvals -- agreement is to `tol`.
+reference computes it with np.linalg.eigvals -- agreement is to `tol`.  A root
+is handed out only when its Collatz-Wielandt bounds certify it; a periodic,
+reducible or defective dense M(u), where they cannot meet, goes to
+np.linalg.eigvals as in the reference.
 """
 import ctypes
 
@@ -115,8 +118,27 @@ def _rho_batch(K, E, a, vals, cols, U, tol, max_iter, dev):
     return rho.view(U, 3).cpu().numpy(), its.cpu().numpy()
 
 
+def _certified(out, tol):
+    """Which rows of (estimate, lower, upper) are certified Perron roots: both
+    Collatz-Wielandt bounds finite and met to tol (include/cvd.h).  Every other
+    estimate is the plain norm ratio, wrong for some periodic / reducible M."""
+    lo, hi = out[:, 1], out[:, 2]
+    with np.errstate(invalid="ignore"):
+        return np.isfinite(lo) & np.isfinite(hi) & (hi - lo <= tol * hi)
+
+
+def _eig_rho(M):
+    """The reference's spectral_radius (alpha_exponent.py:69-76), host numpy."""
+    return float(np.max(np.abs(np.linalg.eigvals(M))))
+
+
 def chernoff_rhos(P1, P2, u_vals, tol=1e-13, max_iter=200_000, device=None, return_bounds=False):
-    """rho(M(u)) for every u in u_vals (GPU), M(u) as in Eq. 7."""
+    """rho(M(u)) for every u in u_vals (GPU), M(u) as in Eq. 7.  Every value is
+    a certified Perron root (bounds met to tol) or, on the dense path where
+    M(u) may be periodic or reducible, the reference's np.linalg.eigvals of that
+    M(u) copied back; the structured M(u) is positive, so an uncertified result
+    there is an error.  return_bounds: (out[U, 3], iters) with out[:, 0] that
+    value and the bounds as the kernel left them."""
     dev = _dev(device)
     u = torch.as_tensor(np.asarray(u_vals, np.float64), device=dev)
     U = len(u)
@@ -134,6 +156,12 @@ def chernoff_rhos(P1, P2, u_vals, tol=1e-13, max_iter=200_000, device=None, retu
                                                  ctypes.c_void_p(a.data_ptr()), ctypes.c_void_p(vals.data_ptr()),
                                                  _stream_ptr(None)))
         out, its = _rho_batch(K, R, a, vals, cols, U, tol, max_iter, dev)
+        bad = np.flatnonzero(~_certified(out, tol))
+        if len(bad):
+            j = int(bad[0])
+            raise _lib.CvdError(f"chernoff_rhos: the Perron root of M(u = {float(u[j])!r}) is not certified after "
+                                f"{int(its[j])} iterations: bracket [{out[j, 1]!r}, {out[j, 2]!r}], "
+                                f"estimate {out[j, 0]!r} (tol = {tol!r}, max_iter = {max_iter})")
     else:
         A1, A2 = np.asarray(P1, np.float64), np.asarray(P2, np.float64)
         if A1.shape != A2.shape or A1.ndim != 3 or A1.shape[0] != A1.shape[1]:
@@ -151,6 +179,8 @@ def chernoff_rhos(P1, P2, u_vals, tol=1e-13, max_iter=200_000, device=None, retu
                                                            ctypes.c_void_p(d2.data_ptr()), ctypes.c_void_p(us.data_ptr()),
                                                            hi - lo, ctypes.c_void_p(vals.data_ptr()), _stream_ptr(None)))
             o, it = _rho_batch(K, K, None, vals, None, hi - lo, tol, max_iter, dev)
+            for j in np.flatnonzero(~_certified(o, tol)):   # periodic / reducible M(u): as the reference
+                o[j, 0] = _eig_rho(vals[j * K * K:(j + 1) * K * K].view(K, K).cpu().numpy())
             outs.append(o)
             itss.append(it)
         out, its = np.concatenate(outs), np.concatenate(itss)
@@ -172,7 +202,9 @@ def compute_error_exponent(P1_ijr, P2_ijr, u_grid=401, tol=1e-13, max_iter=200_0
 
 def spectral_radius(A, tol=1e-13, max_iter=200_000, device=None):
     """rho(A) for a nonnegative square matrix (alpha_exponent.py:69-76): the
-    Perron root, on the GPU.  Matrices with negative entries are rejected (the
+    Perron root, on the GPU, when its Collatz-Wielandt bounds certify it; for a
+    periodic, reducible or defective A, where they do not meet, the reference's
+    np.linalg.eigvals.  Matrices with negative entries are rejected (the
     reference's general eigvals has no GPU counterpart here)."""
     A = np.asarray(A, np.float64)
     if A.ndim != 2 or A.shape[0] != A.shape[1]:
@@ -183,7 +215,7 @@ def spectral_radius(A, tol=1e-13, max_iter=200_000, device=None):
     K = A.shape[0]
     vals = torch.as_tensor(np.ascontiguousarray(A).reshape(-1), device=dev)
     out, _ = _rho_batch(K, K, None, vals, None, 1, tol, max_iter, dev)
-    return float(out[0, 0])
+    return float(out[0, 0]) if _certified(out, tol)[0] else _eig_rho(A)
 
 
 def fit_error_exponent(N_vals, P_e_vals, tail_cap=0.2):

@@ -499,9 +499,14 @@ int cvd_chernoff_build_dense(int32_t K, int32_t R, const double* d_P1, const dou
 /* Perron root of each of U nonnegative K x K matrices M = a 1^T + ELL(vals, cols)
  * (E entries per row; d_cols NULL: dense rows, E = K; d_a NULL: no rank-one part)
  * by power iteration with Collatz-Wielandt bounds: d_rho[3u..3u+2] = (estimate,
- * lower, upper bound) once (upper - lower) <= tol * upper (irreducible M), else
- * once the power-iteration norm ratio is stable to tol/100 (the estimate), or
- * after max_iter iterations (d_iters[u]).  K <= 10000: vectors in LDS, one workgroup per u;
+ * lower, upper bound) once (upper - lower) <= tol * upper (irreducible aperiodic M), else
+ * once the power-iteration norm ratio is stable to tol/100 and the bracket has stopped
+ * shrinking (the estimate), or after max_iter iterations (d_iters[u]).  The estimate in d_rho[3u] is CERTIFIED only
+ * when both bounds are finite and meet that tolerance (then it is their midpoint); in
+ * every other case it is the uncertified norm ratio, which for a periodic, reducible or
+ * defective M can be far from rho -- the caller checks the bounds.  A bracket is never
+ * reported met while some x_i is 0 (the upper bound needs x > 0: it is +inf then).
+ * K <= 10232 (2 K doubles + 128 B within 160 KiB): vectors in LDS, one workgroup per u;
  * larger K (structured form only, d_cols non-NULL): vectors in HBM, one launch per phase. */
 int cvd_spectral_radius(int32_t K, int32_t E, const double* d_a, const double* d_vals,
                         const int32_t* d_cols, int32_t U, double tol, int32_t max_iter, double* d_rho,
