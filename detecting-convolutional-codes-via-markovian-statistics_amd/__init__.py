@@ -20,7 +20,8 @@ from .parity import (  # noqa: F401
 from .blind import (  # noqa: F401
     template_mask, mask_template, mask_extent, parity_sweep, find_parity_checks, identify_code, default_z_min,
 )
-from .decode import decode_capture  # noqa: F401
+from .decode import (PUNCTURE_PATTERNS, decode_capture, decode_capture_punctured, puncture_pattern,  # noqa: F401
+                     punctured_bits, sync_punctured)
 from .exponent import (  # noqa: F401
     TransitionTensor, learn_transition_tensor, chernoff_rhos, compute_error_exponent, spectral_radius,
     fit_error_exponent, EXPONENT_TAG,

@@ -34,7 +34,7 @@
       first check is the generator pair: printed in octal with the scan --code line that
       takes it.  Single-process, like scan.
   ... decode --code C --input FILE [--format bytes|lsb|msb] [--nbits B] [--start S] [--T T]
-             [--out-bits FILE.npy]
+             [--out-bits FILE.npy] [--puncture SPEC [--sync T0]]
       (nothing in the reference) -- what was sent: the hard-decision Viterbi decoder of the
       k = 1 code C over the capture from bit S (cvd_viterbi_decode: the Eq. 4-5 recursion with
       its survivor decisions kept, exact whatever the block split); writes the decoded bits to
@@ -43,6 +43,11 @@
       ber, start_state, end_state, blocks, forward_reruns, trace_fixups.  ber = errors / (n T)
       estimates the channel's crossover probability: printed with the scan line that takes
       it, so the workflow is identify -> decode -> scan.  Single-process, like scan.
+      --puncture SPEC (dvb:2/3 | dvb:3/4 | dvb:5/6 | dvb:7/8 for oct:171,133, or rows per
+      output such as 101/110): the capture carries only the bits the pattern transmits
+      (cvd_viterbi_decode_punctured); --sync T0 first tries the K bit offsets of a period over
+      T0 steps and decodes from the one with the fewest errors.  The CSV gains capture_bits
+      and offset, ber = errors / capture_bits, and no scan line is printed.
 
 Codes: the BASELINE configurations (m2, m6, r23_m4), the demo presets (example:1,
 example:2, demo_script.py:35-52), or oct:G0,G1[,G2] -- k = 1 generators in octal (MSB =
@@ -59,8 +64,9 @@ import re
 import sys
 
 from . import (CONFIG_CODES, DEFAULTS, EXAMPLE_CODES, compute_error_exponent, default_template,
-               decode_capture, find_parity_checks, learn_transition_tensor, octal_to_taps, parity_experiment,
-               parity_vector_to_equation, parity_vectors, run_experiment, scan_capture)
+               decode_capture, decode_capture_punctured, find_parity_checks, learn_transition_tensor, octal_to_taps,
+               parity_experiment, parity_vector_to_equation, parity_vectors, puncture_pattern, run_experiment,
+               scan_capture, sync_punctured)
 
 PROG = "python -m detecting-convolutional-codes-via-markovian-statistics_amd"
 
@@ -180,6 +186,12 @@ def parser():
     d.add_argument("--out-bits", default=None, help=".npy path of the decoded bits (default: <save-dir>/decoded.npy)")
     d.add_argument("--save-dir", default=DEFAULTS["save_dir"])
     d.add_argument("--out", default=None, help="CSV path (default: <save-dir>/decode.csv)")
+    d.add_argument("--puncture", default=None, metavar="SPEC",
+                   help="the capture is punctured: a DVB-S name (dvb:2/3, dvb:3/4, dvb:5/6, dvb:7/8; for oct:171,133) "
+                        "or rows per output over a period's columns, e.g. 101/110")
+    d.add_argument("--sync", type=int, default=None, metavar="T0",
+                   help="with --puncture: try the K bit offsets of a period over the first T0 steps from --start "
+                        "and decode from the best")
 
     c = sub.add_parser("compare", help="P_err figures of both detectors (plots_compare.py)")
     c.add_argument("--hybrid", required=True, help="CSV of the experiment subcommand")
@@ -315,7 +327,26 @@ def cmd_decode(a):
     k, n, m, g1, _ = code_of(a.code)
     if k != 1:
         raise SystemExit(f"decode: {a.code} has k = {k}; the decoder takes k = 1 codes")
-    res = decode_capture(n, m, g1, load_capture(a.input), start=a.start, T=a.T, format=a.format, nbits=a.nbits)
+    if a.sync is not None and a.puncture is None:
+        raise SystemExit("decode: --sync needs --puncture")
+    columns = DECODE_COLUMNS
+    if a.puncture is not None:
+        try:
+            keep = puncture_pattern(a.puncture, n)
+        except ValueError as e:
+            raise SystemExit(f"decode: {e}")
+        capture, offset = load_capture(a.input), 0
+        if a.sync is not None:
+            ranked = sync_punctured(n, m, g1, keep, capture, start=a.start, T=a.sync, format=a.format, nbits=a.nbits)
+            offset = ranked[0]["offset"]
+            print(f"Offsets of a period by errors over {a.sync} steps:",
+                  ", ".join(f"{r['offset']}: {r['errors']}" for r in ranked))
+        res = decode_capture_punctured(n, m, g1, keep, capture, start=a.start + offset, T=a.T, format=a.format,
+                                       nbits=a.nbits)
+        res["offset"] = offset
+        columns = DECODE_COLUMNS + ["capture_bits", "offset"]
+    else:
+        res = decode_capture(n, m, g1, load_capture(a.input), start=a.start, T=a.T, format=a.format, nbits=a.nbits)
     out = a.out or os.path.join(a.save_dir, "decode.csv")
     out_bits = a.out_bits or os.path.join(a.save_dir, "decoded.npy")
     for path in (out, out_bits):
@@ -324,13 +355,18 @@ def cmd_decode(a):
         np.save(f, res["bits"].cpu().numpy())
     with open(out, "w", newline="") as f:
         wr = csv.writer(f)
-        wr.writerow(DECODE_COLUMNS)
-        wr.writerow([repr(res[c]) if c == "ber" else res[c] for c in DECODE_COLUMNS])
+        wr.writerow(columns)
+        wr.writerow([repr(res[c]) if c == "ber" else res[c] for c in columns])
     print(f"Decoded {res['T']} steps: {res['errors']} channel errors, p = {res['ber']!r} "
           f"(states {res['start_state']} -> {res['end_state']}; {res['blocks']} blocks, "
           f"{res['forward_reruns']} forward reruns, {res['trace_fixups']} traceback fix-ups)")
-    print(f"{PROG} scan --code {a.code} --start {a.start} --input {a.input} --format {a.format}"
-          + (f" --nbits {a.nbits}" if a.nbits is not None else "") + f" --p {res['ber']!r} --N N")
+    if a.puncture is not None:
+        # no scan line: the detector's model assumes that every output bit is in the capture
+        print(f"Punctured {a.puncture}: {res['capture_bits']} capture bits from bit {a.start + res['offset']} "
+              f"(offset {res['offset']})")
+    else:
+        print(f"{PROG} scan --code {a.code} --start {a.start} --input {a.input} --format {a.format}"
+              + (f" --nbits {a.nbits}" if a.nbits is not None else "") + f" --p {res['ber']!r} --N N")
     print("Saved bits to", out_bits, "(identify --format lsb --nbits", str(res["T"]) + ")")
     print("Saved results to", out)
     return 0

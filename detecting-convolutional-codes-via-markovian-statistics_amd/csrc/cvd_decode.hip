@@ -41,6 +41,10 @@
 // The channel-error count is the path metric of the traced path: the sum of the blocks'
 // normalisations (D_0 = 0 and D_T(s_T) = 0, and along the decisions D'(s') = D(ps) + d_H
 // holds exactly), integer adds in any order.  No scratch.
+// The kernel arguments, the staging helper, the pattern-independent part of a lane and the
+// forward / join bodies are in cvd_decode_common.h; cvd_decode_punct.hip brings a forward and a
+// join kernel for punctured captures and runs everything else here (cvd::viterbi_setup,
+// cvd::viterbi_launch, cvd_internal.h).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -48,93 +52,29 @@
 
 #include "../../include/cvd.h"
 #include "cvd_capture_bits.h"
+#include "cvd_decode_common.h"
 #include "cvd_internal.h"
 
 namespace {
 
-constexpr int kWave = 64;
-constexpr int kSeg = 1024;                   // steps staged at once (a multiple of 64)
-constexpr int kStageDw = 3 * kSeg / 32 + 4;  // n <= 3: the segment's dwords, alignment slack, funnel word
-
-template <int m>
-struct Shape {
-  static constexpr int S = 1 << m;
-  static constexpr int SPL = S > kWave ? S / kWave : 1;   // states per lane = 64-bit words per decision
-};
-
-struct VArgs {
-  const uint4* cap;
-  int64_t nu4;            // readable 16-byte pieces of the capture
-  int32_t format;
-  int64_t start, T;
-  int32_t L, W, D;
-  int64_t nb;
-  uint32_t gs[3];         // output j: taps of delays 1..m as a mask over the state
-  uint32_t g0;            // bit j: tap of delay 0 of output j
-  uint64_t* dec;          // [nb L][SPL] decision words
-  uint8_t* warm;          // [nb][S]
-  uint8_t* endv;          // [nb][S]
-  int32_t* norm;          // [nb] min of the block's unnormalised end vector
-  int32_t* sst;           // [nb] traced state at step bL
-  int32_t* xs;            // [nb] state at step (b+1)L that block b traces from (certified blocks)
-  int32_t* mis;           // [nb] warm vector of b != forward pass's end vector of b - 1
-  int32_t* unc;           // [nb] block not certified by its lookahead
-  unsigned long long* cnt;  // errors, forward reruns, traceback fix-ups
-  uint32_t* bits;
-  int64_t* stats;
-};
-
-// capture bits [start + n t0, + n cnt) as LSB-first dwords from the dword that holds the first
-template <int n>
-__device__ __forceinline__ void stage_bits(const VArgs& a, int64_t t0, int cnt, uint32_t* st, int lane) {
-  const int64_t p0 = a.start + (int64_t)n * t0;
-  const int64_t g0 = p0 >> 5;
-  const int ndw = ((int)(p0 & 31) + n * cnt + 31) / 32 + 1;    // <= kStageDw
-  for (int i = lane; i < ndw; i += kWave) {
-    const int64_t g = g0 + i;
-    uint32_t v = 0u;
-    if (a.format != CVD_CAPTURE_BYTES) {
-      if ((g >> 2) < a.nu4) {
-        v = reinterpret_cast<const uint32_t*>(a.cap)[g];
-        if (a.format == CVD_CAPTURE_MSB) v = lsb_first(v);
-      }
-    } else {
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        const int64_t piece = 2 * g + h;
-        if (piece < a.nu4) {
-          const uint4 u = a.cap[piece];
-          v |= (byte_bits4(u.x) | (byte_bits4(u.y) << 4) | (byte_bits4(u.z) << 8) | (byte_bits4(u.w) << 12)) << (16 * h);
-        }
-      }
-    }
-    st[i] = v;
-  }
-}
+using namespace cvd::vit;   // kWave, kSeg, kStageDw, Shape, VArgs, stage_bits, LaneBase (cvd_decode_common.h)
 
 template <int m, int n>
-struct Lane {
-  static constexpr int S = Shape<m>::S, SPL = Shape<m>::SPL;
-  int lane;
-  int ps0[SPL], ps1[SPL];          // predecessors of the lane's next states
-  uint32_t bm0[SPL], bm1[SPL];     // their branch metrics: bits 2y..2y+1 = d_H(out(ps_b, u), y)
-
-  __device__ __forceinline__ int state(int i) const { return (lane & (S - 1)) + kWave * i; }
+struct Lane : LaneBase<m> {
+  using LaneBase<m>::S;
+  using LaneBase<m>::SPL;
+  using LaneBase<m>::lane;
+  using LaneBase<m>::ps0;
+  using LaneBase<m>::ps1;
+  using LaneBase<m>::state;
+  uint32_t bm0[SPL], bm1[SPL];     // the predecessors' branch metrics: bits 2y..2y+1 = d_H(out(ps_b, u), y)
 
   __device__ __forceinline__ void init(const VArgs& a) {
-    lane = threadIdx.x;
+    this->init_base();
 #pragma unroll
     for (int i = 0; i < SPL; ++i) {
-      const int s = state(i), u = s & 1;
-      ps0[i] = s >> 1;
-      ps1[i] = ps0[i] | (1 << (m - 1));
-      uint32_t o0 = 0u, o1 = 0u;
-#pragma unroll
-      for (int j = 0; j < n; ++j) {
-        const uint32_t in = (a.g0 >> j) & (uint32_t)u;
-        o0 |= ((in ^ (uint32_t)__builtin_popcount(a.gs[j] & (uint32_t)ps0[i])) & 1u) << j;
-        o1 |= ((in ^ (uint32_t)__builtin_popcount(a.gs[j] & (uint32_t)ps1[i])) & 1u) << j;
-      }
+      const int u = state(i) & 1;
+      const uint32_t o0 = this->template branch_out<n>(a, ps0[i], u), o1 = this->template branch_out<n>(a, ps1[i], u);
       bm0[i] = bm1[i] = 0u;
 #pragma unroll
       for (uint32_t y = 0; y < (1u << n); ++y) {
@@ -142,30 +82,6 @@ struct Lane {
         bm1[i] |= (uint32_t)__builtin_popcount(o1 ^ y) << (2 * y);
       }
     }
-  }
-
-  // D -= min D over the states; returns the min
-  __device__ __forceinline__ int normalise(int (&D)[SPL]) const {
-    int mn = D[0];
-#pragma unroll
-    for (int i = 1; i < SPL; ++i) mn = min(mn, D[i]);
-#pragma unroll
-    for (int k = 1; k < kWave; k <<= 1) mn = min(mn, __shfl_xor(mn, k));
-#pragma unroll
-    for (int i = 0; i < SPL; ++i) D[i] -= mn;
-    return mn;
-  }
-
-  __device__ __forceinline__ void store(uint8_t* vec, const int (&D)[SPL]) const {
-    if (lane < S) {
-#pragma unroll
-      for (int i = 0; i < SPL; ++i) vec[state(i)] = (uint8_t)D[i];
-    }
-  }
-
-  __device__ __forceinline__ void load(const uint8_t* vec, int (&D)[SPL]) const {
-#pragma unroll
-    for (int i = 0; i < SPL; ++i) D[i] = vec[state(i)];
   }
 
   // steps [t0, t1) of Eq. 4-5 on D (not normalised); record: the decision words to
@@ -184,7 +100,7 @@ struct Lane {
     for (int64_t seg = t0; seg < t1; seg += kSeg) {
       const int cnt = (int)min((int64_t)kSeg, t1 - seg);
       __syncthreads();                                   // the previous segment has been read
-      stage_bits<n>(a, seg, cnt, st, lane);
+      stage_bits(a, a.start + (int64_t)n * seg, n * cnt, st, lane);
       __syncthreads();
       uint32_t q = (uint32_t)((a.start + (int64_t)n * seg) & 31);
       int dw = -1;                                       // the staged dwords dw, dw + 1 in SGPRs: y_t is scalar work
@@ -246,20 +162,7 @@ __global__ __launch_bounds__(kWave) void viterbi_forward_kernel(VArgs a) {
   __shared__ int met[Sh::SPL > 1 ? 2 * Sh::S : 1];
   Lane<m, n> ln;
   ln.init(a);
-  const int64_t b = blockIdx.x;
-  const int64_t lo = b * a.L, hi = min(a.T, lo + a.L), t0 = max((int64_t)0, lo - a.W);
-  int D[Sh::SPL];
-#pragma unroll
-  for (int i = 0; i < Sh::SPL; ++i) D[i] = 0;
-  if (t0 < lo) {
-    ln.template run<false>(a, t0, lo, D, nullptr, st, met);
-    ln.normalise(D);
-  }
-  ln.store(a.warm + b * Sh::S, D);
-  ln.template run<true>(a, lo, hi, D, a.dec + lo * Sh::SPL, st, met);
-  const int mn = ln.normalise(D);
-  ln.store(a.endv + b * Sh::S, D);
-  if (ln.lane == 0) a.norm[b] = mn;
+  forward_body(a, ln, st, met);
 }
 
 __global__ void viterbi_compare_kernel(VArgs a, int S) {
@@ -281,31 +184,7 @@ __global__ __launch_bounds__(kWave) void viterbi_join_kernel(VArgs a) {
   __shared__ int met[Sh::SPL > 1 ? 2 * Sh::S : 1];
   Lane<m, n> ln;
   ln.init(a);
-  int D[Sh::SPL];
-  unsigned long long reruns = 0;
-  int64_t b = 1;
-  while (b < a.nb) {
-    const int64_t idx = b + ln.lane;
-    const uint64_t bal = __ballot(idx < a.nb && a.mis[idx] != 0);
-    if (!bal) { b += kWave; continue; }
-    b += __builtin_ctzll(bal);
-    ln.load(a.endv + (b - 1) * Sh::S, D);                // block b - 1 stands: its end vector is the true one
-    while (b < a.nb) {
-      bool diff = false;
-#pragma unroll
-      for (int i = 0; i < Sh::SPL; ++i) diff |= D[i] != (int)a.warm[b * Sh::S + ln.state(i)];
-      if (!__any(diff)) break;
-      ++reruns;
-      const int64_t lo = b * a.L, hi = min(a.T, lo + a.L);
-      ln.template run<true>(a, lo, hi, D, a.dec + lo * Sh::SPL, st, met);
-      const int mn = ln.normalise(D);
-      ln.store(a.endv + b * Sh::S, D);
-      if (ln.lane == 0) a.norm[b] = mn;
-      ++b;
-    }
-    ++b;                                                 // block b joined: scan on behind it
-  }
-  if (ln.lane == 0) a.cnt[1] = reruns;
+  join_body(a, ln, st, met);
 }
 
 __device__ __forceinline__ uint64_t readlane64(uint64_t v, int j) {
@@ -475,6 +354,7 @@ __global__ __launch_bounds__(kWave) void viterbi_fix_kernel(VArgs a) {
     a.stats[6] = a.L;
     a.stats[7] = a.W;
     a.stats[8] = a.D;
+    if (a.period) a.stats[9] = a.span;                   // cvd_viterbi_decode_punctured's int64[10]
   }
 }
 
@@ -487,13 +367,15 @@ __global__ __launch_bounds__(kWave) void viterbi_fix_kernel(VArgs a) {
     }                                                                                     \
   } while (0)
 
-int invalid(const char* what) {
-  cvd::set_error(std::string("viterbi_decode: ") + what);
+constexpr const char* kWho = "viterbi_decode";
+
+int invalid(const char* who, const char* what) {
+  cvd::set_error(std::string(who) + ": " + what);
   return CVD_E_INVALID;
 }
 
-int unsupported(const char* what) {
-  cvd::set_error(std::string("viterbi_decode: ") + what);
+int unsupported(const char* who, const char* what) {
+  cvd::set_error(std::string(who) + ": " + what);
   return CVD_E_UNSUPPORTED;
 }
 
@@ -523,35 +405,46 @@ Layout layout_of(int m, int64_t T, int64_t L) {
 }
 
 // 0 if block is acceptable (resolving 0 to the default), else the error
-int resolve_block(int32_t block, int32_t* L) {
+int resolve_block(const char* who, int32_t block, int32_t* L) {
   if (block == 0) block = CVD_VITERBI_BLOCK;
-  if (block < 32 || block % 32) return invalid("block must be 0 (default) or a multiple of 32, at least 32");
+  if (block < 32 || block % 32) return invalid(who, "block must be 0 (default) or a multiple of 32, at least 32");
   *L = block;
   return CVD_OK;
 }
 
-template <int n>
-int launch_all(int m, const VArgs& a, hipStream_t st) {
-  using K = void (*)(VArgs);
+using Kern = void (*)(VArgs);
 #define CVD_V_ROW(KERN) {KERN<1, n>, KERN<2, n>, KERN<3, n>, KERN<4, n>, KERN<5, n>, KERN<6, n>, KERN<7, n>, KERN<8, n>}
-  static const K fwd[8] = CVD_V_ROW(viterbi_forward_kernel);
-  static const K join[8] = CVD_V_ROW(viterbi_join_kernel);
+template <int n>
+Kern forward_of(int m) {
+  static const Kern fwd[8] = CVD_V_ROW(viterbi_forward_kernel);
+  return fwd[m - 1];
+}
+template <int n>
+Kern join_of(int m) {
+  static const Kern join[8] = CVD_V_ROW(viterbi_join_kernel);
+  return join[m - 1];
+}
 #undef CVD_V_ROW
-  static const K look[8] = {viterbi_look_kernel<1>, viterbi_look_kernel<2>, viterbi_look_kernel<3>,
-                            viterbi_look_kernel<4>, viterbi_look_kernel<5>, viterbi_look_kernel<6>,
-                            viterbi_look_kernel<7>, viterbi_look_kernel<8>};
-  static const K trace[8] = {viterbi_trace_kernel<1>, viterbi_trace_kernel<2>, viterbi_trace_kernel<3>,
-                             viterbi_trace_kernel<4>, viterbi_trace_kernel<5>, viterbi_trace_kernel<6>,
-                             viterbi_trace_kernel<7>, viterbi_trace_kernel<8>};
-  static const K fix[8] = {viterbi_fix_kernel<1>, viterbi_fix_kernel<2>, viterbi_fix_kernel<3>, viterbi_fix_kernel<4>,
-                           viterbi_fix_kernel<5>, viterbi_fix_kernel<6>, viterbi_fix_kernel<7>, viterbi_fix_kernel<8>};
+
+}  // namespace
+
+int cvd::viterbi_launch(int m, const VArgs& a, void (*fwd)(VArgs), void (*join)(VArgs), void* stream) {
+  static const Kern look[8] = {viterbi_look_kernel<1>, viterbi_look_kernel<2>, viterbi_look_kernel<3>,
+                               viterbi_look_kernel<4>, viterbi_look_kernel<5>, viterbi_look_kernel<6>,
+                               viterbi_look_kernel<7>, viterbi_look_kernel<8>};
+  static const Kern trace[8] = {viterbi_trace_kernel<1>, viterbi_trace_kernel<2>, viterbi_trace_kernel<3>,
+                                viterbi_trace_kernel<4>, viterbi_trace_kernel<5>, viterbi_trace_kernel<6>,
+                                viterbi_trace_kernel<7>, viterbi_trace_kernel<8>};
+  static const Kern fix[8] = {viterbi_fix_kernel<1>, viterbi_fix_kernel<2>, viterbi_fix_kernel<3>, viterbi_fix_kernel<4>,
+                              viterbi_fix_kernel<5>, viterbi_fix_kernel<6>, viterbi_fix_kernel<7>, viterbi_fix_kernel<8>};
+  hipStream_t st = (hipStream_t)stream;
   HIP_CHECK(hipMemsetAsync(a.cnt, 0, 64, st));
-  hipLaunchKernelGGL(fwd[m - 1], dim3((unsigned)a.nb), dim3(kWave), 0, st, a);
+  hipLaunchKernelGGL(fwd, dim3((unsigned)a.nb), dim3(kWave), 0, st, a);
   HIP_CHECK(hipGetLastError());
   if (a.nb > 1) {
     hipLaunchKernelGGL(viterbi_compare_kernel, dim3((unsigned)((a.nb + 255) / 256)), dim3(256), 0, st, a, 1 << m);
     HIP_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(join[m - 1], dim3(1), dim3(kWave), 0, st, a);
+    hipLaunchKernelGGL(join, dim3(1), dim3(kWave), 0, st, a);
     HIP_CHECK(hipGetLastError());
   }
   hipLaunchKernelGGL(look[m - 1], dim3((unsigned)a.nb), dim3(kWave), 0, st, a);
@@ -563,40 +456,29 @@ int launch_all(int m, const VArgs& a, hipStream_t st) {
   return CVD_OK;
 }
 
-}  // namespace
-
-extern "C" int64_t cvd_viterbi_workspace_bytes(int32_t n, int32_t m, int64_t T, int32_t block) {
-  if (n < 2 || n > 3 || m < 1 || m > 8) return invalid("needs n in 2..3 and m in 1..8");
-  if (T < 0 || T > INT32_MAX) return invalid("T must be 0..2^31 - 1");
-  int32_t L;
-  if (resolve_block(block, &L)) return CVD_E_INVALID;
-  return layout_of(m, std::max<int64_t>(T, 1), L).total;
-}
-
-extern "C" int cvd_viterbi_decode(const cvd_code* code, const void* d_capture, int64_t nbits, int32_t format,
-                                  int64_t start, int64_t T, int32_t block, int32_t warm, int32_t depth,
-                                  uint32_t* d_bits, int64_t* d_stats, void* d_work, void* stream) {
-  if (!code || !code->taps) return invalid("null code");
-  if (code->k != 1 || code->n < 2 || code->n > 3 || code->m < 1 || code->m > 8)
-    return unsupported("needs k = 1, n in 2..3 and m in 1..8");
+int cvd::viterbi_setup(const char* who, const cvd_code* code, const void* d_capture, int64_t nbits, int32_t format,
+                       int64_t start, int64_t T, int64_t span, int32_t block, int32_t warm, int32_t depth,
+                       int32_t warm_default, int32_t depth_default, uint32_t* d_bits, int64_t* d_stats, void* d_work,
+                       VArgs* out, bool* launch) {
+  *launch = false;
   const int n = code->n, m = code->m;
   if (format != CVD_CAPTURE_LSB && format != CVD_CAPTURE_MSB && format != CVD_CAPTURE_BYTES)
-    return invalid("unknown capture format");
-  if (T < 0 || T > INT32_MAX) return invalid("T must be 0..2^31 - 1");
-  if (start < 0 || nbits < 0) return invalid("needs start, nbits >= 0");
+    return invalid(who, "unknown capture format");
+  if (T < 0 || T > INT32_MAX) return invalid(who, "T must be 0..2^31 - 1");
+  if (start < 0 || nbits < 0) return invalid(who, "needs start, nbits >= 0");
   int64_t end;
-  if (__builtin_mul_overflow(T, (int64_t)n, &end) || __builtin_add_overflow(end, start, &end))
-    return invalid("start + n * T overflows int64");
-  if (end > nbits) return invalid("the symbols do not lie inside [0, nbits)");
+  if (span < 0 || __builtin_add_overflow(span, start, &end))
+    return invalid(who, "the position of the last symbol's end overflows int64");
+  if (end > nbits) return invalid(who, "the symbols do not lie inside [0, nbits)");
   int32_t L;
-  if (resolve_block(block, &L)) return CVD_E_INVALID;
-  if (warm < -1) return invalid("warm must be >= 0, or -1 (default)");
-  if (depth < -1) return invalid("depth must be >= 0, or -1 (default)");
-  const int32_t W = warm < 0 ? CVD_VITERBI_WARM(m) : warm, D = depth < 0 ? CVD_VITERBI_DEPTH(m) : depth;
+  if (resolve_block(who, block, &L)) return CVD_E_INVALID;
+  if (warm < -1) return invalid(who, "warm must be >= 0, or -1 (default)");
+  if (depth < -1) return invalid(who, "depth must be >= 0, or -1 (default)");
+  const int32_t W = warm < 0 ? warm_default : warm, D = depth < 0 ? depth_default : depth;
   if (T == 0) return CVD_OK;
   if (!d_capture || !d_bits || !d_stats || !d_work || ((uintptr_t)d_capture & 15) || ((uintptr_t)d_work & 15) ||
       ((uintptr_t)d_bits & 3) || ((uintptr_t)d_stats & 7))
-    return invalid("d_capture, d_work (16-byte aligned), d_bits (4-byte) and d_stats (8-byte) must be non-null");
+    return invalid(who, "d_capture, d_work (16-byte aligned), d_bits (4-byte) and d_stats (8-byte) must be non-null");
 
   const Layout y = layout_of(m, T, L);
   VArgs a{};
@@ -604,6 +486,7 @@ extern "C" int cvd_viterbi_decode(const cvd_code* code, const void* d_capture, i
   const int64_t nbytes = format == CVD_CAPTURE_BYTES ? nbits : nbits / 8 + (nbits % 8 != 0);
   a.nu4 = nbytes / 16 + (nbytes % 16 != 0);
   a.format = format; a.start = start; a.T = T; a.L = L; a.W = W; a.D = D; a.nb = y.nb;
+  a.span = span;
   for (int j = 0; j < n; ++j) {
     const uint8_t* t = code->taps + (size_t)j * (m + 1);
     if (t[0] & 1) a.g0 |= 1u << j;
@@ -622,6 +505,34 @@ extern "C" int cvd_viterbi_decode(const cvd_code* code, const void* d_capture, i
   a.cnt = reinterpret_cast<unsigned long long*>(w + y.cnt);
   a.bits = d_bits;
   a.stats = d_stats;
-  hipStream_t st = (hipStream_t)stream;
-  return n == 2 ? launch_all<2>(m, a, st) : launch_all<3>(m, a, st);
+  *out = a;
+  *launch = true;
+  return CVD_OK;
+}
+
+extern "C" int64_t cvd_viterbi_workspace_bytes(int32_t n, int32_t m, int64_t T, int32_t block) {
+  if (n < 2 || n > 3 || m < 1 || m > 8) return invalid(kWho, "needs n in 2..3 and m in 1..8");
+  if (T < 0 || T > INT32_MAX) return invalid(kWho, "T must be 0..2^31 - 1");
+  int32_t L;
+  if (resolve_block(kWho, block, &L)) return CVD_E_INVALID;
+  return layout_of(m, std::max<int64_t>(T, 1), L).total;
+}
+
+extern "C" int cvd_viterbi_decode(const cvd_code* code, const void* d_capture, int64_t nbits, int32_t format,
+                                  int64_t start, int64_t T, int32_t block, int32_t warm, int32_t depth,
+                                  uint32_t* d_bits, int64_t* d_stats, void* d_work, void* stream) {
+  if (!code || !code->taps) return invalid(kWho, "null code");
+  if (code->k != 1 || code->n < 2 || code->n > 3 || code->m < 1 || code->m > 8)
+    return unsupported(kWho, "needs k = 1, n in 2..3 and m in 1..8");
+  const int n = code->n, m = code->m;
+  int64_t span;
+  if (T >= 0 && __builtin_mul_overflow(T, (int64_t)n, &span)) span = -1;
+  if (T < 0) span = 0;                                   // reported as a bad T
+  VArgs a;
+  bool launch;
+  const int rc = cvd::viterbi_setup(kWho, code, d_capture, nbits, format, start, T, span, block, warm, depth,
+                                    CVD_VITERBI_WARM(m), CVD_VITERBI_DEPTH(m), d_bits, d_stats, d_work, &a, &launch);
+  if (rc != CVD_OK || !launch) return rc;
+  return cvd::viterbi_launch(m, a, n == 2 ? forward_of<2>(m) : forward_of<3>(m), n == 2 ? join_of<2>(m) : join_of<3>(m),
+                             stream);
 }

@@ -1,0 +1,185 @@
+// What the two forward passes of the capture decoder share (cvd_decode.hip: every output bit
+// of a step is in the capture; cvd_decode_punct.hip: a puncturing pattern says which are): the
+// kernel arguments, the staging of capture bits into LDS, and the part of a lane's state that
+// does not depend on how y_t is read.  Device code; include after <hip/hip_runtime.h>.
+#pragma once
+#include <stdint.h>
+
+#include "../../include/cvd.h"
+#include "cvd_capture_bits.h"
+
+namespace cvd {
+namespace vit {
+
+constexpr int kWave = 64;
+constexpr int kSeg = 1024;                   // steps staged at once (a multiple of 64)
+constexpr int kStageDw = 3 * kSeg / 32 + 4;  // n <= 3: the segment's dwords, alignment slack, funnel word
+
+template <int m>
+struct Shape {
+  static constexpr int S = 1 << m;
+  static constexpr int SPL = S > kWave ? S / kWave : 1;   // states per lane = 64-bit words per decision
+};
+
+struct VArgs {
+  const uint4* cap;
+  int64_t nu4;            // readable 16-byte pieces of the capture
+  int32_t format;
+  int64_t start, T;
+  int32_t L, W, D;
+  int64_t nb;
+  uint32_t gs[3];         // output j: taps of delays 1..m as a mask over the state
+  uint32_t g0;            // bit j: tap of delay 0 of output j
+  uint64_t* dec;          // [nb L][SPL] decision words
+  uint8_t* warm;          // [nb][S]
+  uint8_t* endv;          // [nb][S]
+  int32_t* norm;          // [nb] min of the block's unnormalised end vector
+  int32_t* sst;           // [nb] traced state at step bL
+  int32_t* xs;            // [nb] state at step (b+1)L that block b traces from (certified blocks)
+  int32_t* mis;           // [nb] warm vector of b != forward pass's end vector of b - 1
+  int32_t* unc;           // [nb] block not certified by its lookahead
+  unsigned long long* cnt;  // errors, forward reruns, traceback fix-ups
+  uint32_t* bits;
+  int64_t* stats;
+  // the puncturing pattern (cvd_decode_punct.hip; period = 0: none, stats[9] is not written)
+  int64_t span;           // stats[9]: pos(T) - start, the capture bits consumed
+  int32_t period, K;      // columns, and the capture bits of one period
+  uint64_t pmask;         // bits 4c..4c+3: keep[c]
+  uint64_t ppre[2];       // byte c: pre[c], the capture bits of a period before column c
+};
+
+// capture bits [p0, p0 + span) as LSB-first dwords from the dword that holds the first, and one
+// more (the funnel word); span <= 3 kSeg
+__device__ __forceinline__ void stage_bits(const VArgs& a, int64_t p0, int span, uint32_t* st, int lane) {
+  const int64_t g0 = p0 >> 5;
+  const int ndw = ((int)(p0 & 31) + span + 31) / 32 + 1;       // <= kStageDw
+  for (int i = lane; i < ndw; i += kWave) {
+    const int64_t g = g0 + i;
+    uint32_t v = 0u;
+    if (a.format != CVD_CAPTURE_BYTES) {
+      if ((g >> 2) < a.nu4) {
+        v = reinterpret_cast<const uint32_t*>(a.cap)[g];
+        if (a.format == CVD_CAPTURE_MSB) v = lsb_first(v);
+      }
+    } else {
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const int64_t piece = 2 * g + h;
+        if (piece < a.nu4) {
+          const uint4 u = a.cap[piece];
+          v |= (byte_bits4(u.x) | (byte_bits4(u.y) << 4) | (byte_bits4(u.z) << 8) | (byte_bits4(u.w) << 12)) << (16 * h);
+        }
+      }
+    }
+    st[i] = v;
+  }
+}
+
+// lane = next state: its predecessors, and the metric vector's normalisation, loads and stores
+template <int m>
+struct LaneBase {
+  static constexpr int S = Shape<m>::S, SPL = Shape<m>::SPL;
+  int lane;
+  int ps0[SPL], ps1[SPL];          // predecessors of the lane's next states
+
+  __device__ __forceinline__ int state(int i) const { return (lane & (S - 1)) + kWave * i; }
+
+  __device__ __forceinline__ void init_base() {
+    lane = threadIdx.x;
+#pragma unroll
+    for (int i = 0; i < SPL; ++i) {
+      ps0[i] = state(i) >> 1;
+      ps1[i] = ps0[i] | (1 << (m - 1));
+    }
+  }
+
+  // the n output bits of the branch from state ps with input u
+  template <int n>
+  __device__ __forceinline__ uint32_t branch_out(const VArgs& a, int ps, int u) const {
+    uint32_t o = 0u;
+#pragma unroll
+    for (int j = 0; j < n; ++j) {
+      const uint32_t in = (a.g0 >> j) & (uint32_t)u;
+      o |= ((in ^ (uint32_t)__builtin_popcount(a.gs[j] & (uint32_t)ps)) & 1u) << j;
+    }
+    return o;
+  }
+
+  // D -= min D over the states; returns the min
+  __device__ __forceinline__ int normalise(int (&D)[SPL]) const {
+    int mn = D[0];
+#pragma unroll
+    for (int i = 1; i < SPL; ++i) mn = min(mn, D[i]);
+#pragma unroll
+    for (int k = 1; k < kWave; k <<= 1) mn = min(mn, __shfl_xor(mn, k));
+#pragma unroll
+    for (int i = 0; i < SPL; ++i) D[i] -= mn;
+    return mn;
+  }
+
+  __device__ __forceinline__ void store(uint8_t* vec, const int (&D)[SPL]) const {
+    if (lane < S) {
+#pragma unroll
+      for (int i = 0; i < SPL; ++i) vec[state(i)] = (uint8_t)D[i];
+    }
+  }
+
+  __device__ __forceinline__ void load(const uint8_t* vec, int (&D)[SPL]) const {
+#pragma unroll
+    for (int i = 0; i < SPL; ++i) D[i] = vec[state(i)];
+  }
+};
+
+// The forward kernel's and the join kernel's bodies around a lane type whose
+// run<record>(a, t0, t1, D, dec, st, met) does steps [t0, t1) of Eq. 4-5.
+template <class LaneT>
+__device__ __forceinline__ void forward_body(const VArgs& a, LaneT& ln, uint32_t* st, int* met) {
+  constexpr int S = LaneT::S, SPL = LaneT::SPL;
+  const int64_t b = blockIdx.x;
+  const int64_t lo = b * a.L, hi = min(a.T, lo + a.L), t0 = max((int64_t)0, lo - a.W);
+  int D[SPL];
+#pragma unroll
+  for (int i = 0; i < SPL; ++i) D[i] = 0;
+  if (t0 < lo) {
+    ln.template run<false>(a, t0, lo, D, nullptr, st, met);
+    ln.normalise(D);
+  }
+  ln.store(a.warm + b * S, D);
+  ln.template run<true>(a, lo, hi, D, a.dec + lo * SPL, st, met);
+  const int mn = ln.normalise(D);
+  ln.store(a.endv + b * S, D);
+  if (ln.lane == 0) a.norm[b] = mn;
+}
+
+template <class LaneT>
+__device__ __forceinline__ void join_body(const VArgs& a, LaneT& ln, uint32_t* st, int* met) {
+  constexpr int S = LaneT::S, SPL = LaneT::SPL;
+  int D[SPL];
+  unsigned long long reruns = 0;
+  int64_t b = 1;
+  while (b < a.nb) {
+    const int64_t idx = b + ln.lane;
+    const uint64_t bal = __ballot(idx < a.nb && a.mis[idx] != 0);
+    if (!bal) { b += kWave; continue; }
+    b += __builtin_ctzll(bal);
+    ln.load(a.endv + (b - 1) * S, D);                    // block b - 1 stands: its end vector is the true one
+    while (b < a.nb) {
+      bool diff = false;
+#pragma unroll
+      for (int i = 0; i < SPL; ++i) diff |= D[i] != (int)a.warm[b * S + ln.state(i)];
+      if (!__any(diff)) break;
+      ++reruns;
+      const int64_t lo = b * a.L, hi = min(a.T, lo + a.L);
+      ln.template run<true>(a, lo, hi, D, a.dec + lo * SPL, st, met);
+      const int mn = ln.normalise(D);
+      ln.store(a.endv + b * S, D);
+      if (ln.lane == 0) a.norm[b] = mn;
+      ++b;
+    }
+    ++b;                                                 // block b joined: scan on behind it
+  }
+  if (ln.lane == 0) a.cnt[1] = reruns;
+}
+
+}  // namespace vit
+}  // namespace cvd

@@ -10,6 +10,8 @@
 #include "cvd_common.h"
 #include "cvd_keys.h"
 
+struct cvd_code;   // include/cvd.h
+
 struct cvd_model {
   cvd::CodeDesc dec;          // decoder trellis (G1; Pd_plotter.py:188 "decoder is fixed to H1")
   int32_t kind = 0;           // 0 dense (BFS index, reference-exact), 1 sparse (learned states)
@@ -225,5 +227,21 @@ int device_learn_sparse(const CodeDesc& dec, int64_t L, int64_t burn, uint64_t s
 int device_learn_dense(const CodeDesc& dec, const std::vector<int32_t>& next, int64_t S, int64_t L, int64_t burn,
                        uint64_t seed, double p, int device, void* stream, std::vector<int64_t>& cnt_out,
                        LearnStats* stats);
+
+// Capture decoder (cvd_decode.hip), for its punctured entry point (cvd_decode_punct.hip), which
+// brings its own forward and join kernels and shares everything else.
+namespace vit {
+struct VArgs;   // cvd_decode_common.h
+}
+// cvd_viterbi_decode's argument checks behind the code shape and the workspace layout, with the
+// errors naming `who`: the T steps read `span` capture bits from `start` (-1: an int64 overflow
+// on the way to it), warm / depth -1 resolve to warm_default / depth_default.  CVD_OK with
+// *launch = false at T == 0, else `a` is filled in (the pattern fields zero).
+int viterbi_setup(const char* who, const struct ::cvd_code* code, const void* d_capture, int64_t nbits, int32_t format,
+                  int64_t start, int64_t T, int64_t span, int32_t block, int32_t warm, int32_t depth,
+                  int32_t warm_default, int32_t depth_default, uint32_t* d_bits, int64_t* d_stats, void* d_work,
+                  vit::VArgs* a, bool* launch);
+// memset, fwd (one wave per block), compare, join (one wave), look, trace, fix on `stream`
+int viterbi_launch(int m, const vit::VArgs& a, void (*fwd)(vit::VArgs), void (*join)(vit::VArgs), void* stream);
 
 }  // namespace cvd

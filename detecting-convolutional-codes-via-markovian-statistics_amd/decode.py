@@ -11,6 +11,10 @@ the counters say how often the speculative blocks had to be redone.  No CPU fall
 The workflow on a capture: identify (which code, which phase) -> decode (the data, p) ->
 scan --p p.  The decoded bits are a format="lsb" capture themselves and can go straight back
 into parity_sweep / find_parity_checks, e.g. when an outer code is present.
+
+Punctured captures (DVB-S, 802.11a: a periodic pattern leaves output bits out) go through
+cvd_viterbi_decode_punctured (csrc/cvd_decode_punct.hip): puncture_pattern names the pattern,
+decode_capture_punctured decodes, sync_punctured finds where the periods begin.
 """
 import ctypes
 
@@ -87,3 +91,152 @@ def decode_capture(n, m, gen, capture, start=0, T=None, format="bytes", nbits=No
     return {"bits": bits, "T": T, "errors": int(s[0]), "ber": s[0] / (n * T) if T else 0.0,
             "start_state": int(s[4]), "end_state": int(s[5]), "blocks": int(s[1]), "forward_reruns": int(s[2]),
             "trace_fixups": int(s[3]), "block": int(s[6]), "warm": int(s[7]), "depth": int(s[8])}
+
+
+# ───────────────────────────── punctured captures ───────────────────────────
+
+# Rows per output over the columns of a period ("101/110": row j, column c), for the code
+# oct:171,133 with output 0 = X (ETSI EN 300 421, DVB-S)
+PUNCTURE_PATTERNS = {
+    "dvb:2/3": "10/11",
+    "dvb:3/4": "101/110",
+    "dvb:5/6": "10101/11010",
+    "dvb:7/8": "1000101/1111010",
+}
+MAX_PERIOD = 16
+# include/cvd.h CVD_VITERBI_PUNCT_WARM_GAIN, CVD_VITERBI_PUNCT_DEPTH_GAIN
+PUNCT_WARM_GAIN = 2
+PUNCT_DEPTH_GAIN = 5
+
+
+def puncture_pattern(spec, n):
+    """The column masks keep[c] of a puncturing pattern (bit j of keep[c]: output j of a step in
+    column c is transmitted) from a list of masks, a string of rows per output ("101/110": row j,
+    column c) or a name in PUNCTURE_PATTERNS.  1 <= period <= 16, every column nonzero."""
+    n = int(n)
+    if isinstance(spec, str):
+        rows = PUNCTURE_PATTERNS.get(spec, spec).split("/")
+        if len(rows) != n or len({len(r) for r in rows}) != 1 or any(set(r) - set("01") for r in rows):
+            raise ValueError(f"puncture pattern {spec!r}: needs {n} rows of 0/1 of one length, or one of "
+                             f"{sorted(PUNCTURE_PATTERNS)}")
+        keep = [sum((rows[j][c] == "1") << j for j in range(n)) for c in range(len(rows[0]))]
+    else:
+        keep = [int(v) for v in spec]
+    if not 1 <= len(keep) <= MAX_PERIOD:
+        raise ValueError(f"puncture pattern: the period must be 1..{MAX_PERIOD}, not {len(keep)}")
+    for v in keep:
+        if v <= 0 or v >> n:
+            raise ValueError(f"puncture pattern: column mask {v} must be nonzero and below 2^{n}")
+    return keep
+
+
+def punctured_bits(T, keep):
+    """pos(T) - start of include/cvd.h: the capture bits that T steps of the pattern consume."""
+    T = int(T)
+    cnt = [bin(int(v)).count("1") for v in keep]
+    return (T // len(cnt)) * sum(cnt) + sum(cnt[:T % len(cnt)])
+
+
+def punctured_steps(bits, keep):
+    """The largest T with punctured_bits(T, keep) <= bits."""
+    cnt = [bin(int(v)).count("1") for v in keep]
+    if bits <= 0:
+        return 0
+    T, left = (bits // sum(cnt)) * len(cnt), bits % sum(cnt)
+    for c in cnt:
+        if c > left:
+            break
+        left -= c
+        T += 1
+    return T
+
+
+def default_warm_punctured(m, n, period, K):
+    """include/cvd.h CVD_VITERBI_PUNCT_WARM."""
+    return (default_warm(m) * (K + PUNCT_WARM_GAIN * (n * period - K)) + K - 1) // K
+
+
+def default_depth_punctured(m, n, period, K):
+    """include/cvd.h CVD_VITERBI_PUNCT_DEPTH."""
+    return (default_depth(m) * (K + PUNCT_DEPTH_GAIN * (n * period - K)) + K - 1) // K
+
+
+def decode_capture_punctured(n, m, gen, keep, capture, start=0, T=None, format="bytes", nbits=None, block=None,
+                             warm=None, depth=None, device=None):
+    """cvd_viterbi_decode_punctured: decode_capture over a capture that carries only the output
+    bits that the puncturing pattern `keep` (anything puncture_pattern takes) transmits; the
+    erased outputs do not count in the path distance.  Step t finds its kept bits at capture
+    bit start + punctured_bits(t, keep).  T=None: as many steps as fit from `start`.  Returns
+    decode_capture's dict with capture_bits = punctured_bits(T, keep) added and ber = errors /
+    capture_bits; warm and depth default to default_warm_punctured / default_depth_punctured."""
+    dev = device if isinstance(device, torch.device) else _require_gpu(device)
+    n, m, start = int(n), int(m), int(start)
+    code = as_code(gen, m, 1, n)
+    keep = puncture_pattern(keep, n)
+    period, K = len(keep), punctured_bits(len(keep), keep)
+    cap, fmt, nbits = capture_buffer(capture, format, nbits, dev)
+    if T is None:
+        T = punctured_steps(nbits - start, keep) if start >= 0 else 0
+    T = int(T)
+    if T < 0:
+        raise ValueError("T must be >= 0")
+    if T > MAX_T:
+        raise ValueError(f"T = {T}: one call decodes at most 2^31 - 1 steps")
+    blk = 0 if block is None else int(block)
+    wrm = -1 if warm is None else int(warm)
+    dep = -1 if depth is None else int(depth)
+    if (block is not None and blk <= 0) or (warm is not None and wrm < 0) or (depth is not None and dep < 0):
+        raise ValueError("needs block > 0 (a multiple of 32), warm >= 0 and depth >= 0")
+    L = _lib.lib()
+    kbytes = bytes(keep)
+    wbytes = int(L.cvd_viterbi_workspace_bytes(n, m, T, blk))
+    if wbytes < 0:
+        # the decoder itself names an unsupported code shape
+        _lib.check(L.cvd_viterbi_decode_punctured(code.c, kbytes, period, None, 0, fmt, 0, 0, blk, wrm, dep, None,
+                                                  None, None, None))
+        _lib.check(wbytes)
+    with torch.cuda.device(dev):
+        bits = torch.zeros((T + 31) // 32 * 4, dtype=torch.uint8, device=dev)
+        stats = torch.zeros(10, dtype=torch.int64, device=dev)
+        if T == 0:
+            # no launch: validate the arguments, report the resolved defaults
+            _lib.check(L.cvd_viterbi_decode_punctured(code.c, kbytes, period, ctypes.c_void_p(cap.data_ptr()), nbits,
+                                                      fmt, start, 0, blk, wrm, dep, None, None, None, _stream_ptr()))
+            s = [0, 0, 0, 0, 0, 0, blk or DEFAULT_BLOCK,
+                 default_warm_punctured(m, n, period, K) if wrm < 0 else wrm,
+                 default_depth_punctured(m, n, period, K) if dep < 0 else dep, 0]
+        else:
+            free = torch.cuda.mem_get_info(dev)[0]
+            if wbytes > free:
+                raise MemoryError(f"decode_capture_punctured: the workspace of T = {T} steps (m = {m}) is {wbytes} "
+                                  f"bytes, {free} bytes of device memory are free: decode the capture in pieces")
+            work = torch.empty(wbytes, dtype=torch.uint8, device=dev)
+            _lib.check(L.cvd_viterbi_decode_punctured(code.c, kbytes, period, ctypes.c_void_p(cap.data_ptr()), nbits,
+                                                      fmt, start, T, blk, wrm, dep, ctypes.c_void_p(bits.data_ptr()),
+                                                      ctypes.c_void_p(stats.data_ptr()),
+                                                      ctypes.c_void_p(work.data_ptr()), _stream_ptr()))
+            s = stats.cpu().tolist()     # synchronises: cap and work may be freed on return
+    return {"bits": bits, "T": T, "errors": int(s[0]), "ber": s[0] / s[9] if T else 0.0,
+            "start_state": int(s[4]), "end_state": int(s[5]), "blocks": int(s[1]), "forward_reruns": int(s[2]),
+            "trace_fixups": int(s[3]), "block": int(s[6]), "warm": int(s[7]), "depth": int(s[8]),
+            "capture_bits": int(s[9])}
+
+
+def sync_punctured(n, m, gen, keep, capture, start=0, T=1000, format="bytes", nbits=None, block=None, warm=None,
+                   depth=None, device=None):
+    """Where do the puncturing periods begin?  Runs decode_capture_punctured over the first T
+    steps from each of the K bit offsets of a period (K = the capture bits of one period): from
+    capture bit start + o, o = 0..K-1.  Returns the K result dicts, each with `offset`, ranked
+    by (errors ascending, offset ascending): the path distance is small at the right offset and
+    large elsewhere.  K decoder calls, no kernel of its own.
+    Some patterns make a code catastrophic, or leave several offsets indistinguishable; the list
+    then shows near-equal error counts.  What the ranking means is the caller's reading, not a
+    verdict of this function."""
+    keep = puncture_pattern(keep, n)
+    res = []
+    for o in range(punctured_bits(len(keep), keep)):
+        r = decode_capture_punctured(n, m, gen, keep, capture, start=int(start) + o, T=T, format=format, nbits=nbits,
+                                     block=block, warm=warm, depth=depth, device=device)
+        r["offset"] = o
+        res.append(r)
+    return sorted(res, key=lambda r: (r["errors"], r["offset"]))

@@ -480,6 +480,54 @@ int cvd_viterbi_decode(const cvd_code* code, const void* d_capture, int64_t nbit
                        int64_t start, int64_t T, int32_t block, int32_t warm, int32_t depth,
                        uint32_t* d_bits, int64_t* d_stats, void* d_work, void* stream);
 
+/* The same decoder over a punctured capture (nothing in the reference): DVB-S and 802.11a send
+ * (133,171) at rate 2/3 ... 7/8 by leaving output bits out in a periodic pattern.  A hard-bit
+ * capture has no value for an erased bit, so the pattern goes into the decoder: a step reads
+ * its transmitted bits where the pattern puts them and the erased outputs do not count.
+ * Everything that is not restated here is cvd_viterbi_decode's: the code shapes and
+ * CVD_E_UNSUPPORTED, the capture formats with their alignment and 16-byte readability rule,
+ * states and branches, the tie rule, the end-state rule, the traceback, d_bits, block / warm /
+ * depth (0 / -1 / -1 = default), the definitions of stats[0..8] block for block, and the
+ * workspace, cvd_viterbi_workspace_bytes(n, m, T, block) (its layout does not depend on the
+ * pattern).
+ * Pattern: keep[c], 0 <= c < period, 1 <= period <= 16: bit j of keep[c] says that output j
+ * of a step in column c was transmitted; step t is in column t mod period.  Every keep[c] is
+ * nonzero and has no bit at or above n.  keep is a host pointer, copied in at the call.
+ * Bit positions (all 64-bit): pre[c] = sum_{c' < c} popcount(keep[c']), K = pre[period],
+ *   pos(t) = start + (t div period)*K + pre[t mod period];
+ * the kept outputs of step t, j ascending, are capture bits pos(t), pos(t)+1, ...; y_t has
+ * those bits in their positions j and zeros elsewhere.
+ * Metric: in the forward recursion d_H(out, y_t) becomes
+ *   popcount((out ^ y_t) & keep[t mod period]),
+ * and errors counts over the transmitted bits only.  Relative metrics still fit a byte: any
+ * state is reached from any other in m steps of at most n kept bits each, so D <= n*m holds
+ * as before.
+ * d_stats: int64[10]; [0..8] as above, [9] = pos(T) - start, the capture bits consumed (the
+ * channel's crossover probability is estimated by errors / stats[9]).
+ * Defaults of warm and depth: erased bits make survivors merge later.  With e = n*period - K
+ * erased bits per period the unpunctured defaults grow by the factor 1 + GAIN * e / K, rounded
+ * up (GAIN = 1 is the scaling by the inverse of the kept fraction, n*period/K; the gains are
+ * measured at rates 3/4 and 7/8; without erasures the defaults are
+ * cvd_viterbi_decode's): */
+#define CVD_VITERBI_PUNCT_WARM_GAIN 2
+#define CVD_VITERBI_PUNCT_DEPTH_GAIN 5
+#define CVD_VITERBI_PUNCT_WARM(m, n, period, K) \
+  ((CVD_VITERBI_WARM(m) * ((K) + CVD_VITERBI_PUNCT_WARM_GAIN * ((n) * (period) - (K))) + (K) - 1) / (K))
+#define CVD_VITERBI_PUNCT_DEPTH(m, n, period, K) \
+  ((CVD_VITERBI_DEPTH(m) * ((K) + CVD_VITERBI_PUNCT_DEPTH_GAIN * ((n) * (period) - (K))) + (K) - 1) / (K))
+/* Consistency: with every keep[c] == 2^n - 1, at any period, the call returns
+ * cvd_viterbi_decode's bits and stats[0..8] exactly (at the same block, warm and depth, or at
+ * the defaults, which are then cvd_viterbi_decode's), and stats[9] == n*T.
+ * CVD_E_INVALID, before the device is touched, cvd_last_error() naming
+ * viterbi_decode_punctured, for: every case cvd_viterbi_decode lists (with pos(T) in the
+ * place of start + n*T); null keep; period outside 1..16; a zero column; a bit at or above n;
+ * pos(T) > nbits, or an int64 overflow on the way to pos(T).  T == 0: CVD_OK, nothing written.
+ * Kernels: csrc/cvd_decode_punct.hip (forward, join), csrc/cvd_decode.hip (the rest). */
+int cvd_viterbi_decode_punctured(const cvd_code* code, const uint8_t* keep, int32_t period,
+                                 const void* d_capture, int64_t nbits, int32_t format,
+                                 int64_t start, int64_t T, int32_t block, int32_t warm, int32_t depth,
+                                 uint32_t* d_bits, int64_t* d_stats, void* d_work, void* stream);
+
 /* ---- error-exponent engine (alpha_exponent.py, Eq. 7) ---------------------
  * Joint counts of (metric state i, received word r) along received streams
  * (pitch = nseq) for steps t >= burn_in, on a dense (enumerated) model with
