@@ -44,7 +44,8 @@
 // The kernel arguments, the staging helper, the pattern-independent part of a lane and the
 // forward / join bodies are in cvd_decode_common.h; cvd_decode_punct.hip brings a forward and a
 // join kernel for punctured captures and runs everything else here (cvd::viterbi_setup,
-// cvd::viterbi_launch, cvd_internal.h).
+// cvd::viterbi_launch, cvd_internal.h); cvd_decode_soft.hip does the same for int8 confidence
+// values, with 16-bit metric vectors of its own (viterbi_launch's `wide`).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -428,7 +429,7 @@ Kern join_of(int m) {
 
 }  // namespace
 
-int cvd::viterbi_launch(int m, const VArgs& a, void (*fwd)(VArgs), void (*join)(VArgs), void* stream) {
+int cvd::viterbi_launch(int m, const VArgs& a, void (*fwd)(VArgs), void (*join)(VArgs), void* stream, bool wide) {
   static const Kern look[8] = {viterbi_look_kernel<1>, viterbi_look_kernel<2>, viterbi_look_kernel<3>,
                                viterbi_look_kernel<4>, viterbi_look_kernel<5>, viterbi_look_kernel<6>,
                                viterbi_look_kernel<7>, viterbi_look_kernel<8>};
@@ -442,7 +443,13 @@ int cvd::viterbi_launch(int m, const VArgs& a, void (*fwd)(VArgs), void (*join)(
   hipLaunchKernelGGL(fwd, dim3((unsigned)a.nb), dim3(kWave), 0, st, a);
   HIP_CHECK(hipGetLastError());
   if (a.nb > 1) {
-    hipLaunchKernelGGL(viterbi_compare_kernel, dim3((unsigned)((a.nb + 255) / 256)), dim3(256), 0, st, a, 1 << m);
+    VArgs c = a;                                         // the compare step's view of the vectors
+    if (wide) {
+      c.warm = reinterpret_cast<uint8_t*>(a.warm16);
+      c.endv = reinterpret_cast<uint8_t*>(a.end16);
+    }
+    hipLaunchKernelGGL(viterbi_compare_kernel, dim3((unsigned)((a.nb + 255) / 256)), dim3(256), 0, st, c,
+                       (wide ? 2 : 1) << m);
     HIP_CHECK(hipGetLastError());
     hipLaunchKernelGGL(join, dim3(1), dim3(kWave), 0, st, a);
     HIP_CHECK(hipGetLastError());

@@ -1,7 +1,9 @@
 // What the two forward passes of the capture decoder share (cvd_decode.hip: every output bit
 // of a step is in the capture; cvd_decode_punct.hip: a puncturing pattern says which are): the
 // kernel arguments, the staging of capture bits into LDS, and the part of a lane's state that
-// does not depend on how y_t is read.  Device code; include after <hip/hip_runtime.h>.
+// does not depend on how y_t is read.  cvd_decode_soft.hip (int8 confidence values, 16-bit
+// metric vectors) shares the kernel arguments and that part of a lane, and brings its own
+// staging and bodies.  Device code; include after <hip/hip_runtime.h>.
 #pragma once
 #include <stdint.h>
 
@@ -46,6 +48,11 @@ struct VArgs {
   int32_t period, K;      // columns, and the capture bits of one period
   uint64_t pmask;         // bits 4c..4c+3: keep[c]
   uint64_t ppre[2];       // byte c: pre[c], the capture bits of a period before column c
+  // the soft decoder's 16-bit metric vectors (cvd_decode_soft.hip: D <= 127 n m; null elsewhere).
+  // Its capture is cap read as int8, one value per byte; endv holds min(D, 255), which is all
+  // that look and fix ask of it (is D zero?).
+  uint16_t* warm16;       // [nb][S]
+  uint16_t* end16;        // [nb][S]
 };
 
 // capture bits [p0, p0 + span) as LSB-first dwords from the dword that holds the first, and one

@@ -1,0 +1,430 @@
+// cvd_viterbi_decode_soft and cvd_soft_depuncture (include/cvd.h) for gfx950: the capture
+// decoder of cvd_decode.hip over one int8 confidence value per channel bit.  Only the forward
+// pass and the join know what a step's metric is made of; compare, look, trace and fix read
+// decision words and are cvd_decode.hip's (cvd::viterbi_launch with wide = true: the metric
+// vectors are 16-bit here, D <= 127 n m).  An erased bit is the value 0, so a punctured soft
+// capture is depunctured by a streaming kernel and decoded like any other.
+//
+// What differs from cvd_decode.hip's Lane::run:
+//   metric    cost(out, t) = sum_j a(v_j) [v_j != 0 and (v_j > 0) != bit j of out], a(v) =
+//             min(|v|, 127).  With corr = sum_j (+-1 by bit j of out) v_j and A_t = sum_j a(v_j),
+//             2 cost = A_t - corr, and A_t is the same for every state: the loop carries
+//             x = 2 D - sum_t A_t, the decisions come from x alone (differences of x are twice
+//             those of D), and one v_dot4c_i32_i8 per branch adds -corr onto the predecessor's
+//             x in place.  At the block edges x - min x is even and halves exactly; the
+//             block's normalisation is (min x + sum_t A_t) / 2.  |x| <= 127 n (L + W) < 2^30.
+//   staging   a segment of kSeg steps copies the 16-byte pieces that hold its n kSeg bytes to
+//             LDS; per 64-step chunk lane j packs step j's n values (-128 clamped to -127)
+//             into a dword and adds their magnitudes to its own partial sum of A (one wave
+//             reduction per run, none per step).
+//   per step  scalar: v_readlane of the chunk's packed dword; vector, per branch, the dot
+//             product with a byte pattern of -+1 (zero above n) accumulating onto x(ps).
+// After fix, one streaming kernel re-encodes d_bits from s_0 and counts the sign disagreements
+// (stats[9]) and the non-erased values (stats[10]).
+// wave64, one wave per block, lane = next state, ds_bpermute for 2^m <= 64 and the
+// double-buffered LDS vector above, as in cvd_decode.hip.  No scratch.
+#include <hip/hip_runtime.h>
+
+#include <string>
+
+#include "../../include/cvd.h"
+#include "cvd_decode_common.h"
+#include "cvd_internal.h"
+
+namespace {
+
+using namespace cvd::vit;
+
+constexpr const char* kWho = "viterbi_decode_soft";
+constexpr const char* kWhoDep = "soft_depuncture";
+constexpr int kSoftStageU4 = 3 * kSeg / 16 + 2;   // n <= 3: the segment's 16-byte pieces and alignment slack
+constexpr int64_t kMaxSpan = 1 << 20;             // block + warm: 2 * 127 * 3 * 2^20 < 2^30
+
+template <int m, int n>
+struct SLane : LaneBase<m> {
+  using LaneBase<m>::S;
+  using LaneBase<m>::SPL;
+  using LaneBase<m>::lane;
+  using LaneBase<m>::ps0;
+  using LaneBase<m>::ps1;
+  using LaneBase<m>::state;
+  int pat0[SPL], pat1[SPL];        // byte j < n: -1 if bit j of the branch's output is 1, else +1; 0 above
+
+  __device__ __forceinline__ static int pattern(uint32_t out) {
+    uint32_t p = 0u;
+#pragma unroll
+    for (int j = 0; j < n; ++j) p |= (((out >> j) & 1u) ? 0xffu : 0x01u) << (8 * j);
+    return (int)p;
+  }
+
+  __device__ __forceinline__ void init(const VArgs& a) {
+    this->init_base();
+#pragma unroll
+    for (int i = 0; i < SPL; ++i) {
+      const int u = state(i) & 1;
+      pat0[i] = pattern(this->template branch_out<n>(a, ps0[i], u));
+      pat1[i] = pattern(this->template branch_out<n>(a, ps1[i], u));
+    }
+  }
+
+  // 2 D as 16-bit D, and the byte min(D, 255) that look and fix test for zero
+  __device__ __forceinline__ void store16(uint16_t* vec, uint8_t* bytes, const int (&X)[SPL]) const {
+    if (lane < S) {
+#pragma unroll
+      for (int i = 0; i < SPL; ++i) {
+        const int d = X[i] >> 1;
+        vec[state(i)] = (uint16_t)d;
+        if (bytes) bytes[state(i)] = (uint8_t)min(d, 255);
+      }
+    }
+  }
+
+  // steps [t0, t1) on x (not normalised); record as in cvd_decode.hip's Lane::run.  Returns the
+  // sum of A_t over the steps.  LDS: st kSoftStageU4 pieces, met 2 S ints (S > 64).
+  template <bool record>
+  __device__ __forceinline__ int run(const VArgs& a, int64_t t0, int64_t t1, int (&X)[SPL], uint64_t* dec, uint4* st,
+                                     int* met) const {
+    uint32_t mlo[SPL], mhi[SPL];                         // lane j: the decision word of the chunk's step j
+#pragma unroll
+    for (int i = 0; i < SPL; ++i) mlo[i] = mhi[i] = 0u;
+    int cur = 0;
+    int asum = 0;                                        // this lane's share of sum A_t
+    const int8_t* sb = reinterpret_cast<const int8_t*>(st);
+    for (int64_t seg = t0; seg < t1; seg += kSeg) {
+      const int cnt = (int)min((int64_t)kSeg, t1 - seg);
+      const int64_t p0 = a.start + (int64_t)n * seg;     // the segment's first value
+      const int64_t g0 = p0 >> 4;
+      const int off = (int)(p0 & 15);
+      const int npc = (off + n * cnt + 15) >> 4;         // <= kSoftStageU4 - 1
+      __syncthreads();                                   // the previous segment has been read
+      for (int i = lane; i < npc; i += kWave) {
+        uint4 v = make_uint4(0u, 0u, 0u, 0u);
+        if (g0 + i < a.nu4) v = a.cap[g0 + i];
+        st[i] = v;
+      }
+      __syncthreads();
+      for (int j0 = 0; j0 < cnt; j0 += kWave) {
+        const int c64 = min(kWave, cnt - j0);
+        int vp = 0;                                      // lane j: the n values of the chunk's step j, packed
+        if (lane < c64) {
+          const int8_t* p = sb + off + n * (j0 + lane);
+#pragma unroll
+          for (int j = 0; j < n; ++j) {
+            const int v = max((int)p[j], -127);
+            asum += abs(v);
+            vp |= (v & 255) << (8 * j);
+          }
+        }
+        for (int jj = 0; jj < c64; ++jj) {
+          const int vs = __builtin_amdgcn_readlane(vp, jj);
+          if constexpr (SPL > 1) {
+#pragma unroll
+            for (int i = 0; i < SPL; ++i) met[cur * S + state(i)] = X[i];
+            __syncthreads();
+          }
+#pragma unroll
+          for (int i = 0; i < SPL; ++i) {
+            int a0, a1;
+            if constexpr (SPL > 1) {
+              a0 = met[cur * S + ps0[i]];
+              a1 = met[cur * S + ps1[i]];
+            } else {
+              a0 = __shfl(X[0], ps0[0]);
+              a1 = __shfl(X[0], ps1[0]);
+            }
+            const int x0 = __builtin_amdgcn_sdot4(pat0[i], vs, a0, false);
+            const int x1 = __builtin_amdgcn_sdot4(pat1[i], vs, a1, false);
+            bool d = x1 < x0;                            // ties keep b = 0
+            X[i] = min(x0, x1);
+            if constexpr (record) {
+              if constexpr (S < kWave) d = d && lane < S;
+              const uint64_t bal = __builtin_amdgcn_ballot_w64(d);
+              if (lane == jj) {
+                mlo[i] = (uint32_t)bal;
+                mhi[i] = (uint32_t)(bal >> 32);
+              }
+            }
+          }
+          cur ^= 1;
+        }
+        if constexpr (record) {
+          if (lane < c64) {
+            uint64_t* p = dec + ((seg - t0) + j0 + lane) * SPL;
+#pragma unroll
+            for (int i = 0; i < SPL; ++i) p[i] = ((uint64_t)mhi[i] << 32) | mlo[i];
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int k = 1; k < kWave; k <<= 1) asum += __shfl_xor(asum, k);
+    return asum;
+  }
+
+  // block b's steps from x = 2 D: decisions, end vector and normalisation
+  __device__ __forceinline__ void block(const VArgs& a, int64_t b, int (&X)[SPL], uint4* st, int* met) const {
+    const int64_t lo = b * a.L, hi = min(a.T, lo + a.L);
+    const int asum = this->template run<true>(a, lo, hi, X, a.dec + lo * SPL, st, met);
+    const int mn = this->normalise(X);
+    store16(a.end16 + b * S, a.endv + b * S, X);
+    if (lane == 0) a.norm[b] = (mn + asum) >> 1;
+  }
+};
+
+// cvd_decode_common.h's forward_body and join_body over 16-bit vectors and the doubled metric
+template <int m, int n>
+__global__ __launch_bounds__(kWave) void viterbi_soft_forward_kernel(VArgs a) {
+  using Sh = Shape<m>;
+  constexpr int S = Sh::S, SPL = Sh::SPL;
+  __shared__ uint4 st[kSoftStageU4];
+  __shared__ int met[SPL > 1 ? 2 * S : 1];
+  SLane<m, n> ln;
+  ln.init(a);
+  const int64_t b = blockIdx.x;
+  const int64_t lo = b * a.L, t0 = max((int64_t)0, lo - a.W);
+  int X[SPL];
+#pragma unroll
+  for (int i = 0; i < SPL; ++i) X[i] = 0;
+  if (t0 < lo) {
+    ln.template run<false>(a, t0, lo, X, nullptr, st, met);
+    ln.normalise(X);
+  }
+  ln.store16(a.warm16 + b * S, nullptr, X);
+  ln.block(a, b, X, st, met);
+}
+
+template <int m, int n>
+__global__ __launch_bounds__(kWave) void viterbi_soft_join_kernel(VArgs a) {
+  using Sh = Shape<m>;
+  constexpr int S = Sh::S, SPL = Sh::SPL;
+  __shared__ uint4 st[kSoftStageU4];
+  __shared__ int met[SPL > 1 ? 2 * S : 1];
+  SLane<m, n> ln;
+  ln.init(a);
+  int X[SPL];
+  unsigned long long reruns = 0;
+  int64_t b = 1;
+  while (b < a.nb) {
+    const int64_t idx = b + ln.lane;
+    const uint64_t bal = __ballot(idx < a.nb && a.mis[idx] != 0);
+    if (!bal) { b += kWave; continue; }
+    b += __builtin_ctzll(bal);
+#pragma unroll
+    for (int i = 0; i < SPL; ++i) X[i] = 2 * (int)a.end16[(b - 1) * S + ln.state(i)];   // block b - 1 stands
+    while (b < a.nb) {
+      bool diff = false;
+#pragma unroll
+      for (int i = 0; i < SPL; ++i) diff |= X[i] != 2 * (int)a.warm16[b * S + ln.state(i)];
+      if (!__any(diff)) break;
+      ++reruns;
+      ln.block(a, b, X, st, met);
+      ++b;
+    }
+    ++b;                                                 // block b joined: scan on behind it
+  }
+  if (ln.lane == 0) a.cnt[1] = reruns;
+}
+
+// stats[9], stats[10] (zeroed before the launch): a thread per step re-encodes the step from
+// the decoded bits -- s_t is the m bits before bit t, those before bit 0 are s_0 = stats[4] --
+// and compares the signs.  At most kCountBlocks blocks, one pair of atomics each (with a pair
+// per wave of a grid of 65,536 blocks, half a million adds onto two addresses, the call over
+// 2^27 steps took 11.4 ms instead of 5.3: DESIGN.md §7.13).
+constexpr int kCountBlocks = 2048;
+
+__global__ __launch_bounds__(256) void viterbi_soft_count_kernel(VArgs a, int m, int n) {
+  __shared__ uint32_t part[2][256 / kWave];
+  const int8_t* v = reinterpret_cast<const int8_t*>(a.cap) + a.start;
+  const uint32_t before = __builtin_bitreverse32((uint32_t)a.stats[4]);   // u_{-d} in bit 32 - d
+  uint32_t err = 0u, seen = 0u;                          // a block sees at most 3 * 2^31 / kCountBlocks values
+  for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < a.T; t += (int64_t)gridDim.x * 256) {
+    const int64_t w = t >> 5;
+    const uint32_t hi = a.bits[w], lo = w ? a.bits[w - 1] : before;
+    const uint64_t q = ((uint64_t)hi << 32) | lo;
+    const uint32_t sh = (uint32_t)(t & 31);
+    const uint32_t r = (uint32_t)(q >> (sh + 32u - (uint32_t)m)) & ((1u << m) - 1u);   // bit i: u_{t-m+i}
+    const uint32_t ps = __builtin_bitreverse32(r) >> (32 - m);                       // bit d-1: u_{t-d}
+    const uint32_t u = (hi >> sh) & 1u;
+    for (int j = 0; j < n; ++j) {
+      const uint32_t o = (((a.g0 >> j) & u) ^ (uint32_t)__builtin_popcount(a.gs[j] & ps)) & 1u;
+      const int x = v[(int64_t)n * t + j];
+      seen += x != 0;
+      err += x != 0 && (uint32_t)(x > 0) != o;
+    }
+  }
+#pragma unroll
+  for (int k = 1; k < kWave; k <<= 1) {
+    err += __shfl_xor(err, k);
+    seen += __shfl_xor(seen, k);
+  }
+  if ((threadIdx.x & (kWave - 1)) == 0) {
+    part[0][threadIdx.x / kWave] = err;
+    part[1][threadIdx.x / kWave] = seen;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    unsigned long long* s = reinterpret_cast<unsigned long long*>(a.stats);
+    err = seen = 0u;
+#pragma unroll
+    for (int i = 0; i < 256 / kWave; ++i) {
+      err += part[0][i];
+      seen += part[1][i];
+    }
+    if (err) atomicAdd(&s[9], (unsigned long long)err);
+    if (seen) atomicAdd(&s[10], (unsigned long long)seen);
+  }
+}
+
+struct DArgs {
+  const int8_t* in;
+  uint32_t* out;
+  int64_t start, total, ndw;   // n T values, in ndw dwords with the padding
+  int32_t period, K, n;
+  uint64_t pmask, ppre[2];     // as in VArgs
+};
+
+// a thread per output dword: four values, each its kept input value or zero
+__global__ __launch_bounds__(256) void soft_depuncture_kernel(DArgs a) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= a.ndw) return;
+  uint32_t word = 0u;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int64_t idx = 4 * i + k;
+    if (idx >= a.total) break;
+    const uint32_t t = a.n == 2 ? (uint32_t)(idx >> 1) : (uint32_t)(idx / 3);
+    const uint32_t j = (uint32_t)(idx - (int64_t)a.n * t);
+    const uint32_t r = t / (uint32_t)a.period, c = t - r * (uint32_t)a.period;
+    const uint32_t keep = (uint32_t)(a.pmask >> (4u * c)) & 7u;
+    if ((keep >> j) & 1u) {
+      const uint32_t pre = (uint32_t)(a.ppre[c >> 3] >> (8u * (c & 7u))) & 255u;
+      const int64_t p = a.start + (int64_t)r * a.K + pre + __builtin_popcount(keep & ((1u << j) - 1u));
+      word |= (uint32_t)(uint8_t)a.in[p] << (8 * k);
+    }
+  }
+  a.out[i] = word;
+}
+
+#define HIP_CHECK(x)                                                                      \
+  do {                                                                                    \
+    hipError_t e_ = (x);                                                                  \
+    if (e_ != hipSuccess) {                                                               \
+      cvd::set_error(std::string("HIP error '") + hipGetErrorString(e_) + "' at " #x);     \
+      return CVD_E_HIP;                                                                   \
+    }                                                                                     \
+  } while (0)
+
+int invalid(const char* who, const char* what) {
+  cvd::set_error(std::string(who) + ": " + what);
+  return CVD_E_INVALID;
+}
+
+int64_t round16(int64_t x) { return (x + 15) / 16 * 16; }
+
+using Kern = void (*)(VArgs);
+#define CVD_V_ROW(KERN) {KERN<1, n>, KERN<2, n>, KERN<3, n>, KERN<4, n>, KERN<5, n>, KERN<6, n>, KERN<7, n>, KERN<8, n>}
+template <int n>
+Kern forward_of(int m) {
+  static const Kern fwd[8] = CVD_V_ROW(viterbi_soft_forward_kernel);
+  return fwd[m - 1];
+}
+template <int n>
+Kern join_of(int m) {
+  static const Kern join[8] = CVD_V_ROW(viterbi_soft_join_kernel);
+  return join[m - 1];
+}
+#undef CVD_V_ROW
+
+}  // namespace
+
+// cvd_viterbi_decode's workspace, then the two arrays of 16-bit vectors
+extern "C" int64_t cvd_viterbi_soft_workspace_bytes(int32_t n, int32_t m, int64_t T, int32_t block) {
+  const int64_t base = cvd_viterbi_workspace_bytes(n, m, T, block);
+  if (base < 0) {
+    const std::string why = cvd::last_error_copy();      // "viterbi_decode: ..."
+    const size_t at = why.find(": ");
+    cvd::set_error(std::string(kWho) + (at == std::string::npos ? ": " + why : why.substr(at)));
+    return base;
+  }
+  const int64_t L = block ? block : CVD_VITERBI_BLOCK, nb = ((T > 0 ? T : 1) + L - 1) / L;
+  return base + 2 * round16(nb * ((int64_t)2 << m));
+}
+
+extern "C" int cvd_viterbi_decode_soft(const cvd_code* code, const int8_t* d_soft, int64_t nvals, int64_t start,
+                                       int64_t T, int32_t block, int32_t warm, int32_t depth, uint32_t* d_bits,
+                                       int64_t* d_stats, void* d_work, void* stream) {
+  if (!code || !code->taps) return invalid(kWho, "null code");
+  if (code->k != 1 || code->n < 2 || code->n > 3 || code->m < 1 || code->m > 8) {
+    cvd::set_error(std::string(kWho) + ": needs k = 1, n in 2..3 and m in 1..8");
+    return CVD_E_UNSUPPORTED;
+  }
+  const int n = code->n, m = code->m;
+  int64_t span;
+  if (T >= 0 && __builtin_mul_overflow(T, (int64_t)n, &span)) span = -1;
+  if (T < 0) span = 0;                                   // reported as a bad T
+  // the doubled metric of a block runs over block + warm steps without normalisation (a bad
+  // block or warm is viterbi_setup's to report)
+  if (block >= 0 && warm >= -1 &&
+      (int64_t)(block ? block : CVD_VITERBI_BLOCK) + (warm < 0 ? CVD_VITERBI_WARM(m) : warm) > kMaxSpan)
+    return invalid(kWho, "block + warm must be at most 2^20");
+  VArgs a;
+  bool launch;
+  // one value per byte: the capture checks are those of a CVD_CAPTURE_BYTES capture of nvals bytes
+  const int rc = cvd::viterbi_setup(kWho, code, d_soft, nvals, CVD_CAPTURE_BYTES, start, T, span, block, warm, depth,
+                                    CVD_VITERBI_WARM(m), CVD_VITERBI_DEPTH(m), d_bits, d_stats, d_work, &a, &launch);
+  if (rc != CVD_OK || !launch) return rc;
+  const int64_t vec = round16(a.nb * ((int64_t)2 << m));
+  char* w = static_cast<char*>(d_work) + cvd_viterbi_workspace_bytes(n, m, T, a.L);
+  a.warm16 = reinterpret_cast<uint16_t*>(w);
+  a.end16 = reinterpret_cast<uint16_t*>(w + vec);
+  const int lrc = cvd::viterbi_launch(m, a, n == 2 ? forward_of<2>(m) : forward_of<3>(m),
+                                      n == 2 ? join_of<2>(m) : join_of<3>(m), stream, true);
+  if (lrc != CVD_OK) return lrc;
+  hipStream_t st = (hipStream_t)stream;
+  HIP_CHECK(hipMemsetAsync(d_stats + 9, 0, 16, st));
+  const int64_t blocks = (T + 255) / 256;
+  hipLaunchKernelGGL(viterbi_soft_count_kernel, dim3((unsigned)(blocks < kCountBlocks ? blocks : kCountBlocks)), dim3(256), 0, st, a,
+                     m, n);
+  HIP_CHECK(hipGetLastError());
+  return CVD_OK;
+}
+
+extern "C" int cvd_soft_depuncture(const int8_t* d_in, int64_t nvals, int64_t start, const uint8_t* keep,
+                                   int32_t period, int32_t n, int64_t T, int8_t* d_out, void* stream) {
+  if (n < 2 || n > 3) return invalid(kWhoDep, "needs n in 2..3");
+  if (!keep) return invalid(kWhoDep, "null keep");
+  if (period < 1 || period > 16) return invalid(kWhoDep, "period must be 1..16");
+  DArgs a{};
+  int pre[17];
+  for (int c = 0; c < period; ++c) {
+    if (keep[c] == 0) return invalid(kWhoDep, "a column of keep is zero: every step transmits at least one value");
+    if (keep[c] >> n) return invalid(kWhoDep, "a column of keep has a bit at or above n");
+    pre[c] = a.K;
+    a.pmask |= (uint64_t)keep[c] << (4 * c);
+    a.ppre[c >> 3] |= (uint64_t)a.K << (8 * (c & 7));
+    a.K += __builtin_popcount(keep[c]);
+  }
+  pre[period] = a.K;
+  if (T < 0 || T > INT32_MAX) return invalid(kWhoDep, "T must be 0..2^31 - 1");
+  if (start < 0 || nvals < 0) return invalid(kWhoDep, "needs start, nvals >= 0");
+  int64_t span = 0, end;
+  if (__builtin_mul_overflow(T / period, (int64_t)a.K, &span) ||
+      __builtin_add_overflow(span, (int64_t)pre[T % period], &span) || __builtin_add_overflow(span, start, &end))
+    return invalid(kWhoDep, "the position of the last value's end overflows int64");
+  if (end > nvals) return invalid(kWhoDep, "the values do not lie inside [0, nvals)");
+  if (T == 0) return CVD_OK;
+  if (!d_in || !d_out || ((uintptr_t)d_out & 15)) return invalid(kWhoDep, "d_in and d_out (16-byte aligned) must be non-null");
+  a.total = (int64_t)n * T;
+  const int64_t nout = round16(a.total);
+  const uintptr_t i0 = (uintptr_t)d_in, o0 = (uintptr_t)d_out;
+  if (i0 < o0 + (uintptr_t)nout && o0 < i0 + (uintptr_t)nvals) return invalid(kWhoDep, "d_out overlaps d_in");
+  a.in = d_in;
+  a.out = reinterpret_cast<uint32_t*>(d_out);
+  a.start = start;
+  a.ndw = nout / 4;
+  a.period = period;
+  a.n = n;
+  hipLaunchKernelGGL(soft_depuncture_kernel, dim3((unsigned)((a.ndw + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
+  HIP_CHECK(hipGetLastError());
+  return CVD_OK;
+}

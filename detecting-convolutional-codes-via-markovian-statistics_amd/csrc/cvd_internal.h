@@ -228,8 +228,9 @@ int device_learn_dense(const CodeDesc& dec, const std::vector<int32_t>& next, in
                        uint64_t seed, double p, int device, void* stream, std::vector<int64_t>& cnt_out,
                        LearnStats* stats);
 
-// Capture decoder (cvd_decode.hip), for its punctured entry point (cvd_decode_punct.hip), which
-// brings its own forward and join kernels and shares everything else.
+// Capture decoder (cvd_decode.hip), for its punctured and soft-decision entry points
+// (cvd_decode_punct.hip, cvd_decode_soft.hip), which bring their own forward and join kernels
+// and share everything else.
 namespace vit {
 struct VArgs;   // cvd_decode_common.h
 }
@@ -241,7 +242,10 @@ int viterbi_setup(const char* who, const struct ::cvd_code* code, const void* d_
                   int64_t start, int64_t T, int64_t span, int32_t block, int32_t warm, int32_t depth,
                   int32_t warm_default, int32_t depth_default, uint32_t* d_bits, int64_t* d_stats, void* d_work,
                   vit::VArgs* a, bool* launch);
-// memset, fwd (one wave per block), compare, join (one wave), look, trace, fix on `stream`
-int viterbi_launch(int m, const vit::VArgs& a, void (*fwd)(vit::VArgs), void (*join)(vit::VArgs), void* stream);
+// memset, fwd (one wave per block), compare, join (one wave), look, trace, fix on `stream`.
+// wide: fwd and join keep 16-bit vectors in a.warm16 / a.end16 (cvd_decode_soft.hip), and the
+// compare step goes over their 2 * 2^m bytes.
+int viterbi_launch(int m, const vit::VArgs& a, void (*fwd)(vit::VArgs), void (*join)(vit::VArgs), void* stream,
+                   bool wide = false);
 
 }  // namespace cvd

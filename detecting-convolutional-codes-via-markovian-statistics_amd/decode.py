@@ -15,9 +15,15 @@ into parity_sweep / find_parity_checks, e.g. when an outer code is present.
 Punctured captures (DVB-S, 802.11a: a periodic pattern leaves output bits out) go through
 cvd_viterbi_decode_punctured (csrc/cvd_decode_punct.hip): puncture_pattern names the pattern,
 decode_capture_punctured decodes, sync_punctured finds where the periods begin.
+
+Soft captures (one int8 confidence value per channel bit, 0 = erased) go through
+cvd_viterbi_decode_soft (csrc/cvd_decode_soft.hip): decode_capture_soft decodes, with keep=...
+after depuncturing on the device (depuncture_soft); soft_from_bits turns hard bits into such a
+capture and sync_punctured_soft is sync_punctured's loop.
 """
 import ctypes
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -240,3 +246,155 @@ def sync_punctured(n, m, gen, keep, capture, start=0, T=1000, format="bytes", nb
         r["offset"] = o
         res.append(r)
     return sorted(res, key=lambda r: (r["errors"], r["offset"]))
+
+
+# ───────────────────────────── soft decisions ───────────────────────────────
+
+def soft_from_bits(bits, amplitude=1):
+    """Hard bits as a soft capture: 0 -> -amplitude, 1 -> +amplitude (int8), 1 <= amplitude <= 127."""
+    amplitude = int(amplitude)
+    if not 1 <= amplitude <= 127:
+        raise ValueError(f"amplitude = {amplitude}: must be 1..127")
+    if isinstance(bits, torch.Tensor):
+        if bool(((bits != 0) & (bits != 1)).any()):
+            raise ValueError("soft_from_bits takes bits: 0 or 1")
+        return ((2 * bits.to(torch.int16) - 1) * amplitude).to(torch.int8)
+    b = np.asarray(bits)
+    if ((b != 0) & (b != 1)).any():
+        raise ValueError("soft_from_bits takes bits: 0 or 1")
+    return ((2 * b.astype(np.int16) - 1) * amplitude).astype(np.int8)
+
+
+def _soft_buffer(soft, device):
+    """(device int8 tensor readable to a multiple of 16 bytes, number of values) of a soft capture
+    given as a numpy array or torch tensor of int8: capture_buffer's rule for its uploads."""
+    if isinstance(soft, np.ndarray):
+        soft = np.ascontiguousarray(soft)
+        soft = torch.from_numpy(soft if soft.flags.writeable else soft.copy())
+    cap = soft
+    if not isinstance(cap, torch.Tensor) or cap.dtype != torch.int8:
+        raise TypeError("a soft capture is a numpy array or torch tensor of int8")
+    cap = cap.reshape(-1)
+    nvals = cap.numel()
+    if cap.device != device or not cap.is_contiguous() or nvals % 16 or cap.data_ptr() % 16:
+        buf = torch.zeros((nvals + 15) // 16 * 16 or 16, dtype=torch.int8, device=device)
+        buf[:nvals].copy_(cap)
+        cap = buf
+    return cap, nvals
+
+
+def _depuncture(L, cap, nvals, start, keep, n, T, dev):
+    """cvd_soft_depuncture into a fresh buffer of n T values rounded up to 16 bytes."""
+    out = torch.empty((n * T + 15) // 16 * 16 or 16, dtype=torch.int8, device=dev)
+    _lib.check(L.cvd_soft_depuncture(ctypes.c_void_p(cap.data_ptr()), nvals, start, bytes(keep), len(keep), n, T,
+                                     ctypes.c_void_p(out.data_ptr()), _stream_ptr()))
+    return out
+
+
+def depuncture_soft(soft, keep, n, start=0, T=None, device=None):
+    """cvd_soft_depuncture: the punctured soft capture `soft` (int8) from value `start` spread out
+    to n values per step, zeros (erasures) where the pattern `keep` (anything puncture_pattern
+    takes) transmits nothing.  T=None: as many steps as fit.  Returns a device int8 tensor of
+    n T values (a view of a buffer padded with zeros to 16 bytes: decode_capture_soft uses it in
+    place)."""
+    dev = device if isinstance(device, torch.device) else _require_gpu(device)
+    n, start = int(n), int(start)
+    keep = puncture_pattern(keep, n)
+    cap, nvals = _soft_buffer(soft, dev)
+    if T is None:
+        T = punctured_steps(nvals - start, keep) if start >= 0 else 0
+    T = int(T)
+    with torch.cuda.device(dev):
+        out = _depuncture(_lib.lib(), cap, nvals, start, keep, n, T, dev)
+        torch.cuda.current_stream().synchronize()        # cap may be freed on return
+    return out[:n * max(T, 0)]
+
+
+def decode_capture_soft(n, m, gen, soft, start=0, T=None, keep=None, block=None, warm=None, depth=None, device=None):
+    """cvd_viterbi_decode_soft over a soft capture (numpy array or torch tensor of int8: v > 0
+    says 1, v < 0 says 0, 0 is an erasure, |v| the confidence): value start + n*t + j belongs to
+    output j of step t.  T=None: as many whole steps as fit from `start`.  Returns
+    decode_capture's dict with metric (the soft distance of the decoded path) and erasures added;
+    errors counts the values whose sign disagrees with the path and ber = errors / (n T -
+    erasures) (0.0 when nothing is left).
+    keep (anything puncture_pattern takes): the capture is punctured, step t finds its kept
+    values at start + punctured_bits(t, keep); it is depunctured on the device
+    (cvd_soft_depuncture: zeros where nothing was sent) and decoded by the same call.  T=None
+    then means as many steps as fit, warm and depth default to default_warm_punctured /
+    default_depth_punctured, and capture_bits = punctured_bits(T, keep) is added."""
+    dev = device if isinstance(device, torch.device) else _require_gpu(device)
+    n, m, start = int(n), int(m), int(start)
+    code = as_code(gen, m, 1, n)
+    if keep is not None:
+        keep = puncture_pattern(keep, n)
+    cap, nvals = _soft_buffer(soft, dev)
+    if T is None:
+        fit = max(0, nvals - start) if start >= 0 else 0
+        T = fit // n if keep is None else punctured_steps(fit, keep)
+    T = int(T)
+    if T < 0:
+        raise ValueError("T must be >= 0")
+    if T > MAX_T:
+        raise ValueError(f"T = {T}: one call decodes at most 2^31 - 1 steps")
+    blk = 0 if block is None else int(block)
+    wrm = -1 if warm is None else int(warm)
+    dep = -1 if depth is None else int(depth)
+    if (block is not None and blk <= 0) or (warm is not None and wrm < 0) or (depth is not None and dep < 0):
+        raise ValueError("needs block > 0 (a multiple of 32), warm >= 0 and depth >= 0")
+    if keep is not None:
+        period, K = len(keep), punctured_bits(len(keep), keep)
+        if wrm < 0:
+            wrm = default_warm_punctured(m, n, period, K)
+        if dep < 0:
+            dep = default_depth_punctured(m, n, period, K)
+    L = _lib.lib()
+    wbytes = int(L.cvd_viterbi_soft_workspace_bytes(n, m, T, blk))
+    if wbytes < 0:
+        # the decoder itself names an unsupported code shape
+        _lib.check(L.cvd_viterbi_decode_soft(code.c, None, 0, 0, 0, blk, wrm, dep, None, None, None, None))
+        _lib.check(wbytes)
+    with torch.cuda.device(dev):
+        bits = torch.zeros((T + 31) // 32 * 4, dtype=torch.uint8, device=dev)
+        stats = torch.zeros(11, dtype=torch.int64, device=dev)
+        if keep is not None:
+            # validates the pattern's range; T == 0: no launch
+            cap, nvals, start = _depuncture(L, cap, nvals, start, keep, n, T, dev), n * T, 0
+        if T == 0:
+            # no launch: validate the arguments, report the resolved defaults
+            _lib.check(L.cvd_viterbi_decode_soft(code.c, ctypes.c_void_p(cap.data_ptr()), nvals, start, 0, blk, wrm,
+                                                 dep, None, None, None, _stream_ptr()))
+            s = [0, 0, 0, 0, 0, 0, blk or DEFAULT_BLOCK, default_warm(m) if wrm < 0 else wrm,
+                 default_depth(m) if dep < 0 else dep, 0, 0]
+        else:
+            free = torch.cuda.mem_get_info(dev)[0]
+            if wbytes > free:
+                raise MemoryError(f"decode_capture_soft: the workspace of T = {T} steps (m = {m}) is {wbytes} bytes, "
+                                  f"{free} bytes of device memory are free: decode the capture in pieces")
+            work = torch.empty(wbytes, dtype=torch.uint8, device=dev)
+            _lib.check(L.cvd_viterbi_decode_soft(code.c, ctypes.c_void_p(cap.data_ptr()), nvals, start, T, blk, wrm,
+                                                 dep, ctypes.c_void_p(bits.data_ptr()),
+                                                 ctypes.c_void_p(stats.data_ptr()), ctypes.c_void_p(work.data_ptr()),
+                                                 _stream_ptr()))
+            s = stats.cpu().tolist()     # synchronises: cap and work may be freed on return
+    res = {"bits": bits, "T": T, "errors": int(s[9]), "ber": s[9] / s[10] if s[10] else 0.0,
+           "start_state": int(s[4]), "end_state": int(s[5]), "blocks": int(s[1]), "forward_reruns": int(s[2]),
+           "trace_fixups": int(s[3]), "block": int(s[6]), "warm": int(s[7]), "depth": int(s[8]),
+           "metric": int(s[0]), "erasures": n * T - int(s[10])}
+    if keep is not None:
+        res["capture_bits"] = punctured_bits(T, keep)
+    return res
+
+
+def sync_punctured_soft(n, m, gen, keep, soft, start=0, T=1000, block=None, warm=None, depth=None, device=None):
+    """sync_punctured over a soft capture: decode_capture_soft(keep=...) over the first T steps
+    from each of the K value offsets of a period, the K result dicts, each with `offset`, ranked
+    by (metric ascending, offset ascending).  What the ranking means is the caller's reading, as
+    there."""
+    keep = puncture_pattern(keep, n)
+    res = []
+    for o in range(punctured_bits(len(keep), keep)):
+        r = decode_capture_soft(n, m, gen, soft, start=int(start) + o, T=T, keep=keep, block=block, warm=warm,
+                                depth=depth, device=device)
+        r["offset"] = o
+        res.append(r)
+    return sorted(res, key=lambda r: (r["metric"], r["offset"]))

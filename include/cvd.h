@@ -25,6 +25,8 @@
  *                             (all 2^B parity templates of a capture at once: histogram + WHT)
  *   (none: the reference keeps no survivor decisions, viterbi_markov.py:139-159)   cvd_viterbi_decode
  *                             (hard-decision Viterbi decoder of a capture: bits, error count, end states)
+ *   (none: the reference's channel is a BSC, viterbi_markov.py:139-159)            cvd_viterbi_decode_soft,
+ *                             (the same decoder over int8 confidence values, 0 = erased) cvd_soft_depuncture
  *   alpha_exponent.py:83-156  learn_transition_tensor (joint counts)              cvd_count_transitions
  *   alpha_exponent.py:159-188 compute_error_exponent: M(u) for a u grid           cvd_chernoff_build(_dense)
  *   alpha_exponent.py:69-76   spectral_radius (Perron root of M(u) >= 0)           cvd_spectral_radius
@@ -527,6 +529,64 @@ int cvd_viterbi_decode_punctured(const cvd_code* code, const uint8_t* keep, int3
                                  const void* d_capture, int64_t nbits, int32_t format,
                                  int64_t start, int64_t T, int32_t block, int32_t warm, int32_t depth,
                                  uint32_t* d_bits, int64_t* d_stats, void* d_work, void* stream);
+
+/* The same decoder over soft decisions (nothing in the reference): a demodulator's confidence
+ * value per channel bit instead of the sliced bit, which costs about 2 dB.  An erased bit is a
+ * value of 0, so a depunctured soft capture (cvd_soft_depuncture below) goes through this one
+ * decoder; it knows nothing about patterns.
+ * Capture: one int8 per channel bit in device memory; value start + n*t + j belongs to output
+ * j of step t, 0 <= t < T.  v > 0: the bit is more likely 1; v < 0: more likely 0; v = 0: an
+ * erasure; -128 is read as -127, so that with a(v) = min(|v|, 127) the contract is symmetric.
+ * d_soft is 16-byte aligned and readable up to nvals rounded up to 16 bytes; nothing at or
+ * past that is read.  Positions are 64-bit.
+ * Metric: in the forward recursion of cvd_viterbi_decode, d_H(out, y_t) becomes
+ *   cost(out, t) = sum_j a(v_{t,j}) * [v_{t,j} != 0 and (v_{t,j} > 0) != bit j of out].
+ * Everything that is not restated here is cvd_viterbi_decode's: the code shapes and
+ * CVD_E_UNSUPPORTED, states and branches, D_0 = 0, the tie rule, the normalisation, the
+ * end-state rule, the traceback, d_bits, block / warm / depth (0 / -1 / -1 = default:
+ * CVD_VITERBI_BLOCK, CVD_VITERBI_WARM(m), CVD_VITERBI_DEPTH(m)) and the definitions of
+ * stats[1..8] block for block.  Relative metrics obey D <= 127*n*m <= 3048 (any state is
+ * reached from any other in m steps of at most 127*n each), so the warm and end vectors are
+ * 16-bit and the workspace has a size function of its own.
+ * d_stats: int64[11], written (not accumulated), 8-byte aligned:
+ *   [0]     the soft distance of the traced path, sum_t cost(out(s_t, u_t), t)
+ *   [1..8]  as in cvd_viterbi_decode
+ *   [9]     hard errors: #{(t, j) : v != 0 and (v > 0) != bit j of out(s_t, u_t)}
+ *   [10]    the non-erased values among the n*T
+ * stats[9] / stats[10] estimates the channel's crossover probability (the p that scan needs);
+ * the soft distance is not that quantity.
+ * Consistency: with every value +-A the call returns cvd_viterbi_decode's bits and
+ * stats[1..8] on the signs, stats[0] = A * errors, stats[9] = errors, stats[10] = n*T; with
+ * zeros at the erased positions, cvd_viterbi_decode_punctured's.
+ * block + warm <= 2^20 (the unnormalised metrics of a block run over block + warm steps;
+ * CVD_E_INVALID above that); the result is exact for everything accepted.
+ * CVD_E_INVALID, before the device is touched, cvd_last_error() naming viterbi_decode_soft,
+ * for: every case cvd_viterbi_decode lists (nvals in the place of nbits, no format); the
+ * block + warm bound; null or misaligned pointers when T > 0 (d_soft, d_work 16-byte, d_bits
+ * 4-byte, d_stats 8-byte aligned).  T == 0: CVD_OK without a launch (nothing is written).
+ * d_work: cvd_viterbi_soft_workspace_bytes(n, m, T, block) bytes, 16-byte aligned
+ * (cvd_viterbi_workspace_bytes and two 16-bit vectors per block; < 0 as that one).
+ * Kernels: csrc/cvd_decode_soft.hip (forward, join, the hard-error count),
+ * csrc/cvd_decode.hip (the rest). */
+int64_t cvd_viterbi_soft_workspace_bytes(int32_t n, int32_t m, int64_t T, int32_t block);
+int cvd_viterbi_decode_soft(const cvd_code* code, const int8_t* d_soft, int64_t nvals,
+                            int64_t start, int64_t T, int32_t block, int32_t warm, int32_t depth,
+                            uint32_t* d_bits, int64_t* d_stats, void* d_work, void* stream);
+/* A punctured soft capture spread out to n values per step, zeros (erasures) where the pattern
+ * transmits nothing.  keep, period and pos(t) exactly as cvd_viterbi_decode_punctured defines
+ * them (n in {2, 3}), with values in the place of bits: for 0 <= t < T,
+ *   d_out[n*t + j] = d_in[pos(t) + rank of j among the kept outputs of keep[t mod period]]
+ * where keep[t mod period] has bit j, and 0 otherwise.  d_out holds n*T values rounded up to
+ * 16 bytes, the padding written as zeros; it is 16-byte aligned and does not overlap d_in
+ * (any alignment; only values inside [0, nvals) are read).
+ * CVD_E_INVALID, before the device is touched, cvd_last_error() naming soft_depuncture, for:
+ * n outside 2..3; null keep; period outside 1..16; a zero column; a bit at or above n;
+ * start < 0, nvals < 0, T < 0 or T > 2^31 - 1; pos(T) > nvals, or an int64 overflow on the way
+ * to it; when T > 0 a null d_in or d_out, a misaligned d_out, or overlapping buffers.
+ * T == 0: CVD_OK, nothing written.  Kernel: csrc/cvd_decode_soft.hip. */
+int cvd_soft_depuncture(const int8_t* d_in, int64_t nvals, int64_t start,
+                        const uint8_t* keep, int32_t period, int32_t n, int64_t T,
+                        int8_t* d_out, void* stream);
 
 /* ---- error-exponent engine (alpha_exponent.py, Eq. 7) ---------------------
  * Joint counts of (metric state i, received word r) along received streams
