@@ -41,11 +41,15 @@
 // The channel-error count is the path metric of the traced path: the sum of the blocks'
 // normalisations (D_0 = 0 and D_T(s_T) = 0, and along the decisions D'(s') = D(ps) + d_H
 // holds exactly), integer adds in any order.  No scratch.
-// The kernel arguments, the staging helper, the pattern-independent part of a lane and the
-// forward / join bodies are in cvd_decode_common.h; cvd_decode_punct.hip brings a forward and a
-// join kernel for punctured captures and runs everything else here (cvd::viterbi_setup,
-// cvd::viterbi_launch, cvd_internal.h); cvd_decode_soft.hip does the same for int8 confidence
-// values, with 16-bit metric vectors of its own (viterbi_launch's `wide`).
+// The kernel arguments, the staging helper, the pattern-independent part of a lane, the step
+// loop (acs_chunk) and the forward / join bodies are in cvd_decode_common.h: this file's Lane
+// brings the branch-metric fields, the staging and the SGPR funnel that y_t is shifted out of.
+// cvd_decode_punct.hip brings a lane, a forward and a join kernel for punctured captures and
+// runs everything else here; cvd_decode_soft.hip does the same for int8 confidence values, whose
+// lane keeps 16-bit metric vectors (`wide`: their place in the workspace and the compare step's
+// width).  The host code the three share is here too, declared in cvd_internal.h: the
+// code-shape check, the packing of a puncturing pattern, the workspace layout, viterbi_setup
+// and viterbi_launch.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -85,18 +89,16 @@ struct Lane : LaneBase<m> {
     }
   }
 
+  __device__ __forceinline__ int cand0(int i, uint32_t y2, int a) const { return a + (int)((bm0[i] >> y2) & 3u); }
+  __device__ __forceinline__ int cand1(int i, uint32_t y2, int a) const { return a + (int)((bm1[i] >> y2) & 3u); }
+
   // steps [t0, t1) of Eq. 4-5 on D (not normalised); record: the decision words to
-  // dec[(t - t0) SPL + i]: lane j keeps the ballot of a 64-step chunk's step j, and after the
-  // chunk the wave stores its 64 words as one contiguous piece (a slot per step in LDS instead,
-  // one ds_write_b64 per step, made the loop LDS-bound: the two ds_bpermute already take two
-  // thirds of the LDS pipe's time).  LDS: st kStageDw dwords, met 2 S ints (S > 64).
+  // dec[(t - t0) SPL + i] (acs_chunk).  Returns 0: D is the metric itself.  LDS: st kStageDw
+  // dwords, met 2 S ints (S > 64).
   template <bool record>
-  __device__ __forceinline__ void run(const VArgs& a, int64_t t0, int64_t t1, int (&D)[SPL], uint64_t* dec,
-                                      uint32_t* st, int* met) const {
+  __device__ __forceinline__ int run(const VArgs& a, int64_t t0, int64_t t1, int (&D)[SPL], uint64_t* dec,
+                                     uint32_t* st, int* met) const {
     constexpr uint32_t ymask = (1u << n) - 1u;
-    uint32_t mlo[SPL], mhi[SPL];                         // lane j: the decision word of the chunk's step j
-#pragma unroll
-    for (int i = 0; i < SPL; ++i) mlo[i] = mhi[i] = 0u;
     int cur = 0;
     for (int64_t seg = t0; seg < t1; seg += kSeg) {
       const int cnt = (int)min((int64_t)kSeg, t1 - seg);
@@ -107,52 +109,19 @@ struct Lane : LaneBase<m> {
       int dw = -1;                                       // the staged dwords dw, dw + 1 in SGPRs: y_t is scalar work
       uint32_t wlo = 0u, whi = 0u;
       for (int j0 = 0; j0 < cnt; j0 += kWave) {
-        const int c64 = min(kWave, cnt - j0);
-        for (int jj = 0; jj < c64; ++jj, q += n) {
+        acs_chunk<record>(*this, min(kWave, cnt - j0), D, cur, met, dec + ((seg - t0) + j0) * SPL, [&](int) {
           if ((int)(q >> 5) != dw) {
             dw = (int)(q >> 5);
             wlo = (uint32_t)__builtin_amdgcn_readfirstlane((int)st[dw]);
             whi = (uint32_t)__builtin_amdgcn_readfirstlane((int)st[dw + 1]);
           }
           const uint32_t y2 = 2u * ((uint32_t)((((uint64_t)whi << 32) | wlo) >> (q & 31u)) & ymask);
-          if constexpr (SPL > 1) {
-#pragma unroll
-            for (int i = 0; i < SPL; ++i) met[cur * S + state(i)] = D[i];
-            __syncthreads();
-          }
-#pragma unroll
-          for (int i = 0; i < SPL; ++i) {
-            int a0, a1;
-            if constexpr (SPL > 1) {
-              a0 = met[cur * S + ps0[i]];
-              a1 = met[cur * S + ps1[i]];
-            } else {
-              a0 = __shfl(D[0], ps0[0]);
-              a1 = __shfl(D[0], ps1[0]);
-            }
-            const int c0 = a0 + (int)((bm0[i] >> y2) & 3u), c1 = a1 + (int)((bm1[i] >> y2) & 3u);
-            bool d = c1 < c0;                            // ties keep b = 0
-            D[i] = min(c0, c1);
-            if constexpr (record) {
-              if constexpr (S < kWave) d = d && lane < S;
-              const uint64_t bal = __builtin_amdgcn_ballot_w64(d);
-              if (lane == jj) {
-                mlo[i] = (uint32_t)bal;
-                mhi[i] = (uint32_t)(bal >> 32);
-              }
-            }
-          }
-          cur ^= 1;
-        }
-        if constexpr (record) {
-          if (lane < c64) {
-            uint64_t* p = dec + ((seg - t0) + j0 + lane) * SPL;
-#pragma unroll
-            for (int i = 0; i < SPL; ++i) p[i] = ((uint64_t)mhi[i] << 32) | mlo[i];
-          }
-        }
+          q += n;
+          return y2;
+        });
       }
     }
+    return 0;
   }
 };
 
@@ -359,35 +328,15 @@ __global__ __launch_bounds__(kWave) void viterbi_fix_kernel(VArgs a) {
   }
 }
 
-#define HIP_CHECK(x)                                                                      \
-  do {                                                                                    \
-    hipError_t e_ = (x);                                                                  \
-    if (e_ != hipSuccess) {                                                               \
-      cvd::set_error(std::string("HIP error '") + hipGetErrorString(e_) + "' at " #x);     \
-      return CVD_E_HIP;                                                                   \
-    }                                                                                     \
-  } while (0)
-
 constexpr const char* kWho = "viterbi_decode";
 
-int invalid(const char* who, const char* what) {
-  cvd::set_error(std::string(who) + ": " + what);
-  return CVD_E_INVALID;
-}
-
-int unsupported(const char* who, const char* what) {
-  cvd::set_error(std::string(who) + ": " + what);
-  return CVD_E_UNSUPPORTED;
-}
-
-int64_t round16(int64_t x) { return (x + 15) / 16 * 16; }
-
 struct Layout {
-  int64_t nb, dec, warm, endv, norm, sst, xs, mis, unc, cnt, total;
+  int64_t nb, dec, warm, endv, norm, sst, xs, mis, unc, cnt, warm16, end16, total;
 };
 
-// T in 1..2^31 - 1, L >= 32: nb L < 2^32, every size far below 2^63
-Layout layout_of(int m, int64_t T, int64_t L) {
+// T in 1..2^31 - 1, L >= 32: nb L < 2^32, every size far below 2^63.  wide: the soft decoder's
+// two arrays of 16-bit vectors behind everything else.
+Layout layout_of(int m, int64_t T, int64_t L, bool wide) {
   const int64_t S = (int64_t)1 << m, spl = S > kWave ? S / kWave : 1;
   Layout y{};
   y.nb = (T + L - 1) / L;
@@ -401,6 +350,10 @@ Layout layout_of(int m, int64_t T, int64_t L) {
   y.mis = off;  off += round16(y.nb * 4);
   y.unc = off;  off += round16(y.nb * 4);
   y.cnt = off;  off += 64;
+  if (wide) {
+    y.warm16 = off; off += round16(y.nb * S * 2);
+    y.end16 = off;  off += round16(y.nb * S * 2);
+  }
   y.total = off;
   return y;
 }
@@ -413,19 +366,7 @@ int resolve_block(const char* who, int32_t block, int32_t* L) {
   return CVD_OK;
 }
 
-using Kern = void (*)(VArgs);
-#define CVD_V_ROW(KERN) {KERN<1, n>, KERN<2, n>, KERN<3, n>, KERN<4, n>, KERN<5, n>, KERN<6, n>, KERN<7, n>, KERN<8, n>}
-template <int n>
-Kern forward_of(int m) {
-  static const Kern fwd[8] = CVD_V_ROW(viterbi_forward_kernel);
-  return fwd[m - 1];
-}
-template <int n>
-Kern join_of(int m) {
-  static const Kern join[8] = CVD_V_ROW(viterbi_join_kernel);
-  return join[m - 1];
-}
-#undef CVD_V_ROW
+CVD_VITERBI_PICK(viterbi_forward_kernel, viterbi_join_kernel)
 
 }  // namespace
 
@@ -463,10 +404,45 @@ int cvd::viterbi_launch(int m, const VArgs& a, void (*fwd)(VArgs), void (*join)(
   return CVD_OK;
 }
 
+int cvd::viterbi_code_shape(const char* who, const cvd_code* code) {
+  if (!code || !code->taps) return invalid(who, "null code");
+  if (code->k != 1 || code->n < 2 || code->n > 3 || code->m < 1 || code->m > 8)
+    return unsupported(who, "needs k = 1, n in 2..3 and m in 1..8");
+  return CVD_OK;
+}
+
+int cvd::viterbi_pack_pattern(const char* who, const char* noun, const uint8_t* keep, int32_t period, int32_t n,
+                              VPattern* out) {
+  if (!keep) return invalid(who, "null keep");
+  if (period < 1 || period > 16) return invalid(who, "period must be 1..16");
+  VPattern p;
+  p.period = period;
+  for (int c = 0; c < period; ++c) {
+    if (keep[c] == 0)
+      return invalid(who, ("a column of keep is zero: every step transmits at least one " + std::string(noun)).c_str());
+    if (keep[c] >> n) return invalid(who, "a column of keep has a bit at or above n");
+    p.pre[c] = p.K;
+    p.pmask |= (uint64_t)keep[c] << (4 * c);
+    p.ppre[c >> 3] |= (uint64_t)p.K << (8 * (c & 7));
+    p.K += __builtin_popcount(keep[c]);
+  }
+  p.pre[period] = p.K;
+  *out = p;
+  return CVD_OK;
+}
+
+int64_t cvd::viterbi_workspace_bytes(const char* who, int32_t n, int32_t m, int64_t T, int32_t block, bool wide) {
+  if (n < 2 || n > 3 || m < 1 || m > 8) return invalid(who, "needs n in 2..3 and m in 1..8");
+  if (T < 0 || T > INT32_MAX) return invalid(who, "T must be 0..2^31 - 1");
+  int32_t L;
+  if (resolve_block(who, block, &L)) return CVD_E_INVALID;
+  return layout_of(m, std::max<int64_t>(T, 1), L, wide).total;
+}
+
 int cvd::viterbi_setup(const char* who, const cvd_code* code, const void* d_capture, int64_t nbits, int32_t format,
                        int64_t start, int64_t T, int64_t span, int32_t block, int32_t warm, int32_t depth,
                        int32_t warm_default, int32_t depth_default, uint32_t* d_bits, int64_t* d_stats, void* d_work,
-                       VArgs* out, bool* launch) {
+                       VArgs* out, bool* launch, bool wide) {
   *launch = false;
   const int n = code->n, m = code->m;
   if (format != CVD_CAPTURE_LSB && format != CVD_CAPTURE_MSB && format != CVD_CAPTURE_BYTES)
@@ -487,7 +463,7 @@ int cvd::viterbi_setup(const char* who, const cvd_code* code, const void* d_capt
       ((uintptr_t)d_bits & 3) || ((uintptr_t)d_stats & 7))
     return invalid(who, "d_capture, d_work (16-byte aligned), d_bits (4-byte) and d_stats (8-byte) must be non-null");
 
-  const Layout y = layout_of(m, T, L);
+  const Layout y = layout_of(m, T, L, wide);
   VArgs a{};
   a.cap = static_cast<const uint4*>(d_capture);
   const int64_t nbytes = format == CVD_CAPTURE_BYTES ? nbits : nbits / 8 + (nbits % 8 != 0);
@@ -510,6 +486,10 @@ int cvd::viterbi_setup(const char* who, const cvd_code* code, const void* d_capt
   a.mis = reinterpret_cast<int32_t*>(w + y.mis);
   a.unc = reinterpret_cast<int32_t*>(w + y.unc);
   a.cnt = reinterpret_cast<unsigned long long*>(w + y.cnt);
+  if (wide) {
+    a.warm16 = reinterpret_cast<uint16_t*>(w + y.warm16);
+    a.end16 = reinterpret_cast<uint16_t*>(w + y.end16);
+  }
   a.bits = d_bits;
   a.stats = d_stats;
   *out = a;
@@ -518,19 +498,13 @@ int cvd::viterbi_setup(const char* who, const cvd_code* code, const void* d_capt
 }
 
 extern "C" int64_t cvd_viterbi_workspace_bytes(int32_t n, int32_t m, int64_t T, int32_t block) {
-  if (n < 2 || n > 3 || m < 1 || m > 8) return invalid(kWho, "needs n in 2..3 and m in 1..8");
-  if (T < 0 || T > INT32_MAX) return invalid(kWho, "T must be 0..2^31 - 1");
-  int32_t L;
-  if (resolve_block(kWho, block, &L)) return CVD_E_INVALID;
-  return layout_of(m, std::max<int64_t>(T, 1), L).total;
+  return cvd::viterbi_workspace_bytes(kWho, n, m, T, block, false);
 }
 
 extern "C" int cvd_viterbi_decode(const cvd_code* code, const void* d_capture, int64_t nbits, int32_t format,
                                   int64_t start, int64_t T, int32_t block, int32_t warm, int32_t depth,
                                   uint32_t* d_bits, int64_t* d_stats, void* d_work, void* stream) {
-  if (!code || !code->taps) return invalid(kWho, "null code");
-  if (code->k != 1 || code->n < 2 || code->n > 3 || code->m < 1 || code->m > 8)
-    return unsupported(kWho, "needs k = 1, n in 2..3 and m in 1..8");
+  if (const int rc = cvd::viterbi_code_shape(kWho, code)) return rc;
   const int n = code->n, m = code->m;
   int64_t span;
   if (T >= 0 && __builtin_mul_overflow(T, (int64_t)n, &span)) span = -1;
@@ -540,6 +514,7 @@ extern "C" int cvd_viterbi_decode(const cvd_code* code, const void* d_capture, i
   const int rc = cvd::viterbi_setup(kWho, code, d_capture, nbits, format, start, T, span, block, warm, depth,
                                     CVD_VITERBI_WARM(m), CVD_VITERBI_DEPTH(m), d_bits, d_stats, d_work, &a, &launch);
   if (rc != CVD_OK || !launch) return rc;
-  return cvd::viterbi_launch(m, a, n == 2 ? forward_of<2>(m) : forward_of<3>(m), n == 2 ? join_of<2>(m) : join_of<3>(m),
-                             stream);
+  Kern fwd, join;
+  pick(m, n, &fwd, &join);
+  return cvd::viterbi_launch(m, a, fwd, join, stream);
 }

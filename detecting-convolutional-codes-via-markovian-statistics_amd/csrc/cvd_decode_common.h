@@ -1,14 +1,22 @@
-// What the two forward passes of the capture decoder share (cvd_decode.hip: every output bit
-// of a step is in the capture; cvd_decode_punct.hip: a puncturing pattern says which are): the
-// kernel arguments, the staging of capture bits into LDS, and the part of a lane's state that
-// does not depend on how y_t is read.  cvd_decode_soft.hip (int8 confidence values, 16-bit
-// metric vectors) shares the kernel arguments and that part of a lane, and brings its own
-// staging and bodies.  Device code; include after <hip/hip_runtime.h>.
+// What the three forward passes of the capture decoder share (cvd_decode.hip: every output bit
+// of a step is in the capture; cvd_decode_punct.hip: a puncturing pattern says which are;
+// cvd_decode_soft.hip: an int8 confidence value per bit): the kernel arguments, the staging of
+// capture bits into LDS, the part of a lane's state that does not depend on how y_t is read,
+// the step loop of Eq. 4-5 (acs_chunk: metric exchange, add-compare-select with the tie rule,
+// decision words) around the lane type's candidate metric, and the forward and join kernels'
+// bodies around its run().  A lane type brings init, run (staging, the symbol of a step, what
+// persists between chunks), cand0 / cand1, and, where its vectors are not 8-bit, the four vector
+// members and norm_of.  Behind the device code: what the three files' host code shares beside
+// the functions that cvd_internal.h declares (HIP_CHECK, invalid / unsupported, round16, the
+// kernel table).  Include after <hip/hip_runtime.h>.
 #pragma once
 #include <stdint.h>
 
+#include <string>
+
 #include "../../include/cvd.h"
 #include "cvd_capture_bits.h"
+#include "cvd_internal.h"
 
 namespace cvd {
 namespace vit {
@@ -135,15 +143,95 @@ struct LaneBase {
 #pragma unroll
     for (int i = 0; i < SPL; ++i) D[i] = vec[state(i)];
   }
+
+  // the bodies' view of block b's vectors (8-bit here), and of its normalisation: mn = min D
+  // before normalising, sum = what run returned
+  __device__ __forceinline__ void store_warm(const VArgs& a, int64_t b, const int (&D)[SPL]) const { store(a.warm + b * S, D); }
+  __device__ __forceinline__ void store_end(const VArgs& a, int64_t b, const int (&D)[SPL]) const { store(a.endv + b * S, D); }
+  __device__ __forceinline__ void load_end(const VArgs& a, int64_t b, int (&D)[SPL]) const { load(a.endv + b * S, D); }
+  __device__ __forceinline__ bool differs_from_warm(const VArgs& a, int64_t b, const int (&D)[SPL]) const {
+    bool diff = false;
+#pragma unroll
+    for (int i = 0; i < SPL; ++i) diff |= D[i] != (int)a.warm[b * S + state(i)];
+    return diff;
+  }
+  __device__ __forceinline__ static int norm_of(int mn, int sum) { return mn; }
 };
 
-// The forward kernel's and the join kernel's bodies around a lane type whose
-// run<record>(a, t0, t1, D, dec, st, met) does steps [t0, t1) of Eq. 4-5.
-template <class LaneT>
-__device__ __forceinline__ void forward_body(const VArgs& a, LaneT& ln, uint32_t* st, int* met) {
+// At most 64 steps of Eq. 4-5 on D (not normalised): symbol(jj) is the wave-uniform received
+// symbol of the chunk's step jj, ln.cand0 / cand1(i, y, a) the metric of next state state(i)
+// through its predecessor ps0[i] / ps1[i], whose metric is a.  The predecessors' metrics come
+// over ds_bpermute, for S > 64 through the double-buffered LDS vector met (2 S ints; cur says
+// which half is next).  record: lane j keeps the decision word of step j (the ballot of
+// "predecessor 1 strictly smaller", the lanes that repeat states masked out) and after the
+// chunk the wave stores its c64 words to dec[j SPL + i] as one contiguous piece (a slot per
+// step in LDS instead, one ds_write_b64 per step, made the loop LDS-bound: the two ds_bpermute
+// already take two thirds of the LDS pipe's time).
+template <bool record, class LaneT, class Symbol>
+__device__ __forceinline__ void acs_chunk(const LaneT& ln, int c64, int (&D)[LaneT::SPL], int& cur, int* met,
+                                          uint64_t* dec, Symbol symbol) {
   constexpr int S = LaneT::S, SPL = LaneT::SPL;
+  uint32_t mlo[SPL], mhi[SPL];
+#pragma unroll
+  for (int i = 0; i < SPL; ++i) mlo[i] = mhi[i] = 0u;
+  for (int jj = 0; jj < c64; ++jj) {
+    const auto y = symbol(jj);
+    if constexpr (SPL > 1) {
+#pragma unroll
+      for (int i = 0; i < SPL; ++i) met[cur * S + ln.state(i)] = D[i];
+      __syncthreads();
+    }
+#pragma unroll
+    for (int i = 0; i < SPL; ++i) {
+      int a0, a1;
+      if constexpr (SPL > 1) {
+        a0 = met[cur * S + ln.ps0[i]];
+        a1 = met[cur * S + ln.ps1[i]];
+      } else {
+        a0 = __shfl(D[0], ln.ps0[0]);
+        a1 = __shfl(D[0], ln.ps1[0]);
+      }
+      const int c0 = ln.cand0(i, y, a0), c1 = ln.cand1(i, y, a1);
+      bool d = c1 < c0;                                  // ties keep b = 0
+      D[i] = min(c0, c1);
+      if constexpr (record) {
+        if constexpr (S < kWave) d = d && ln.lane < S;
+        const uint64_t bal = __builtin_amdgcn_ballot_w64(d);
+        if (ln.lane == jj) {
+          mlo[i] = (uint32_t)bal;
+          mhi[i] = (uint32_t)(bal >> 32);
+        }
+      }
+    }
+    cur ^= 1;
+  }
+  if constexpr (record) {
+    if (ln.lane < c64) {
+#pragma unroll
+      for (int i = 0; i < SPL; ++i) dec[ln.lane * SPL + i] = ((uint64_t)mhi[i] << 32) | mlo[i];
+    }
+  }
+}
+
+// The forward kernel's and the join kernel's bodies around a lane type whose
+// run<record>(a, t0, t1, D, dec, st, met) does steps [t0, t1) of Eq. 4-5 and returns what
+// enters the normalisation beside min D (0 where D is the metric itself).
+
+// block b's steps from the vector at its start: decisions, end vector and normalisation
+template <class LaneT, class St>
+__device__ __forceinline__ void block_body(const VArgs& a, LaneT& ln, int64_t b, int (&D)[LaneT::SPL], St* st, int* met) {
+  const int64_t lo = b * a.L, hi = min(a.T, lo + a.L);
+  const int sum = ln.template run<true>(a, lo, hi, D, a.dec + lo * LaneT::SPL, st, met);
+  const int mn = ln.normalise(D);
+  ln.store_end(a, b, D);
+  if (ln.lane == 0) a.norm[b] = ln.norm_of(mn, sum);
+}
+
+template <class LaneT, class St>
+__device__ __forceinline__ void forward_body(const VArgs& a, LaneT& ln, St* st, int* met) {
+  constexpr int SPL = LaneT::SPL;
   const int64_t b = blockIdx.x;
-  const int64_t lo = b * a.L, hi = min(a.T, lo + a.L), t0 = max((int64_t)0, lo - a.W);
+  const int64_t lo = b * a.L, t0 = max((int64_t)0, lo - a.W);
   int D[SPL];
 #pragma unroll
   for (int i = 0; i < SPL; ++i) D[i] = 0;
@@ -151,17 +239,13 @@ __device__ __forceinline__ void forward_body(const VArgs& a, LaneT& ln, uint32_t
     ln.template run<false>(a, t0, lo, D, nullptr, st, met);
     ln.normalise(D);
   }
-  ln.store(a.warm + b * S, D);
-  ln.template run<true>(a, lo, hi, D, a.dec + lo * SPL, st, met);
-  const int mn = ln.normalise(D);
-  ln.store(a.endv + b * S, D);
-  if (ln.lane == 0) a.norm[b] = mn;
+  ln.store_warm(a, b, D);
+  block_body(a, ln, b, D, st, met);
 }
 
-template <class LaneT>
-__device__ __forceinline__ void join_body(const VArgs& a, LaneT& ln, uint32_t* st, int* met) {
-  constexpr int S = LaneT::S, SPL = LaneT::SPL;
-  int D[SPL];
+template <class LaneT, class St>
+__device__ __forceinline__ void join_body(const VArgs& a, LaneT& ln, St* st, int* met) {
+  int D[LaneT::SPL];
   unsigned long long reruns = 0;
   int64_t b = 1;
   while (b < a.nb) {
@@ -169,24 +253,51 @@ __device__ __forceinline__ void join_body(const VArgs& a, LaneT& ln, uint32_t* s
     const uint64_t bal = __ballot(idx < a.nb && a.mis[idx] != 0);
     if (!bal) { b += kWave; continue; }
     b += __builtin_ctzll(bal);
-    ln.load(a.endv + (b - 1) * S, D);                    // block b - 1 stands: its end vector is the true one
+    ln.load_end(a, b - 1, D);                            // block b - 1 stands: its end vector is the true one
     while (b < a.nb) {
-      bool diff = false;
-#pragma unroll
-      for (int i = 0; i < SPL; ++i) diff |= D[i] != (int)a.warm[b * S + ln.state(i)];
-      if (!__any(diff)) break;
+      if (!__any(ln.differs_from_warm(a, b, D))) break;
       ++reruns;
-      const int64_t lo = b * a.L, hi = min(a.T, lo + a.L);
-      ln.template run<true>(a, lo, hi, D, a.dec + lo * SPL, st, met);
-      const int mn = ln.normalise(D);
-      ln.store(a.endv + b * S, D);
-      if (ln.lane == 0) a.norm[b] = mn;
+      block_body(a, ln, b, D, st, met);
       ++b;
     }
     ++b;                                                 // block b joined: scan on behind it
   }
   if (ln.lane == 0) a.cnt[1] = reruns;
 }
+
+// ── host side ──
+
+#define HIP_CHECK(x)                                                                      \
+  do {                                                                                    \
+    hipError_t e_ = (x);                                                                  \
+    if (e_ != hipSuccess) {                                                               \
+      cvd::set_error(std::string("HIP error '") + hipGetErrorString(e_) + "' at " #x);     \
+      return CVD_E_HIP;                                                                   \
+    }                                                                                     \
+  } while (0)
+
+inline int invalid(const char* who, const char* what) {
+  cvd::set_error(std::string(who) + ": " + what);
+  return CVD_E_INVALID;
+}
+
+inline int unsupported(const char* who, const char* what) {
+  cvd::set_error(std::string(who) + ": " + what);
+  return CVD_E_UNSUPPORTED;
+}
+
+inline int64_t round16(int64_t x) { return (x + 15) / 16 * 16; }
+
+// pick(m, n, &fwd, &join): a file's forward and join kernels of a code shape (m in 1..8, n in 2..3)
+using Kern = void (*)(VArgs);
+#define CVD_V_ROW(KERN, n) {KERN<1, n>, KERN<2, n>, KERN<3, n>, KERN<4, n>, KERN<5, n>, KERN<6, n>, KERN<7, n>, KERN<8, n>}
+#define CVD_VITERBI_PICK(FWD, JOIN)                                          \
+  void pick(int m, int n, Kern* fwd, Kern* join) {                           \
+    static const Kern f[2][8] = {CVD_V_ROW(FWD, 2), CVD_V_ROW(FWD, 3)};      \
+    static const Kern j[2][8] = {CVD_V_ROW(JOIN, 2), CVD_V_ROW(JOIN, 3)};    \
+    *fwd = f[n - 2][m - 1];                                                  \
+    *join = j[n - 2][m - 1];                                                 \
+  }
 
 }  // namespace vit
 }  // namespace cvd

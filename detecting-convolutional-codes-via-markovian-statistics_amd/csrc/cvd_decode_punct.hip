@@ -4,8 +4,10 @@
 // pos(t) = start + (t div period) K + pre[c] and leaves the erased outputs out of the Hamming
 // distance.  Compare, look, trace and fix read decision words and are cvd_decode.hip's
 // (cvd::viterbi_launch); the join kernel reruns blocks with this file's forward recursion.
+// The step loop and the two kernels' bodies are cvd_decode_common.h's (acs_chunk, forward_body,
+// join_body), the pattern's checks and packing cvd_decode.hip's (cvd::viterbi_pack_pattern).
 //
-// What differs from cvd_decode.hip's Lane::run:
+// What PLane brings where cvd_decode.hip's Lane has its funnel and 2-bit metric fields:
 //   staging   a segment of kSeg steps covers the bits [pos(seg), pos(seg + cnt)), never more
 //             than n cnt; once its dwords are in LDS the lanes resolve the pattern, 16 steps
 //             each: the step's column (a segment, a warm-up, a block or a rerun may begin in
@@ -62,15 +64,20 @@ struct PLane : LaneBase<m> {
     }
   }
 
-  // steps [t0, t1) of Eq. 4-5 with the pattern's metric on D (not normalised); record and met as
-  // in cvd_decode.hip's Lane::run.  LDS: st kPunctStageDw dwords: the segment's capture dwords,
-  // then a byte per step, y_t | keep << 4.
+  // y: a step's byte, y_t | keep << 4
+  __device__ __forceinline__ int cand0(int i, uint32_t y, int a) const {
+    return __builtin_popcount((o0[i] ^ y) & (y >> 4) & 7u) + a;
+  }
+  __device__ __forceinline__ int cand1(int i, uint32_t y, int a) const {
+    return __builtin_popcount((o1[i] ^ y) & (y >> 4) & 7u) + a;
+  }
+
+  // steps [t0, t1) of Eq. 4-5 with the pattern's metric on D (not normalised); record, met and
+  // the result as in cvd_decode.hip's Lane::run.  LDS: st kPunctStageDw dwords: the segment's
+  // capture dwords, then a byte per step, y_t | keep << 4.
   template <bool record>
-  __device__ __forceinline__ void run(const VArgs& a, int64_t t0, int64_t t1, int (&D)[SPL], uint64_t* dec,
-                                      uint32_t* st, int* met) const {
-    uint32_t mlo[SPL], mhi[SPL];                         // lane j: the decision word of the chunk's step j
-#pragma unroll
-    for (int i = 0; i < SPL; ++i) mlo[i] = mhi[i] = 0u;
+  __device__ __forceinline__ int run(const VArgs& a, int64_t t0, int64_t t1, int (&D)[SPL], uint64_t* dec,
+                                     uint32_t* st, int* met) const {
     int cur = 0;
     uint32_t* sy = st + kStageDw;
     const uint32_t per = (uint32_t)a.period, q64 = (uint32_t)kWave / per, r64 = (uint32_t)kWave - q64 * per;
@@ -112,54 +119,18 @@ struct PLane : LaneBase<m> {
       int dw = -1;                                       // eight steps' bytes in an SGPR pair: y_t, keep are scalar work
       uint32_t wlo = 0u, whi = 0u;
       for (int j0 = 0; j0 < cnt; j0 += kWave) {
-        const int c64 = min(kWave, cnt - j0);
-        for (int jj = 0; jj < c64; ++jj) {
+        acs_chunk<record>(*this, min(kWave, cnt - j0), D, cur, met, dec + ((seg - t0) + j0) * SPL, [&](int jj) {
           const int j = j0 + jj;
           if ((j >> 3) != dw) {
             dw = j >> 3;
             wlo = (uint32_t)__builtin_amdgcn_readfirstlane((int)sy[2 * dw]);
             whi = (uint32_t)__builtin_amdgcn_readfirstlane((int)sy[2 * dw + 1]);
           }
-          const uint32_t code = (uint32_t)((((uint64_t)whi << 32) | wlo) >> (8u * ((uint32_t)j & 7u)));
-          const uint32_t y = code & 7u, keep = (code >> 4) & 7u;
-          if constexpr (SPL > 1) {
-#pragma unroll
-            for (int i = 0; i < SPL; ++i) met[cur * S + state(i)] = D[i];
-            __syncthreads();
-          }
-#pragma unroll
-          for (int i = 0; i < SPL; ++i) {
-            int a0, a1;
-            if constexpr (SPL > 1) {
-              a0 = met[cur * S + ps0[i]];
-              a1 = met[cur * S + ps1[i]];
-            } else {
-              a0 = __shfl(D[0], ps0[0]);
-              a1 = __shfl(D[0], ps1[0]);
-            }
-            const int b0 = __builtin_popcount((o0[i] ^ y) & keep) + a0, b1 = __builtin_popcount((o1[i] ^ y) & keep) + a1;
-            bool d = b1 < b0;                            // ties keep b = 0
-            D[i] = min(b0, b1);
-            if constexpr (record) {
-              if constexpr (S < kWave) d = d && lane < S;
-              const uint64_t bal = __builtin_amdgcn_ballot_w64(d);
-              if (lane == jj) {
-                mlo[i] = (uint32_t)bal;
-                mhi[i] = (uint32_t)(bal >> 32);
-              }
-            }
-          }
-          cur ^= 1;
-        }
-        if constexpr (record) {
-          if (lane < c64) {
-            uint64_t* p = dec + ((seg - t0) + j0 + lane) * SPL;
-#pragma unroll
-            for (int i = 0; i < SPL; ++i) p[i] = ((uint64_t)mhi[i] << 32) | mlo[i];
-          }
-        }
+          return (uint32_t)((((uint64_t)whi << 32) | wlo) >> (8u * ((uint32_t)j & 7u)));
+        });
       }
     }
+    return 0;
   }
 };
 
@@ -185,24 +156,7 @@ __global__ __launch_bounds__(kWave) void viterbi_punct_join_kernel(VArgs a) {
   join_body(a, ln, st, met);
 }
 
-int invalid(const char* what) {
-  cvd::set_error(std::string(kWho) + ": " + what);
-  return CVD_E_INVALID;
-}
-
-using Kern = void (*)(VArgs);
-#define CVD_V_ROW(KERN) {KERN<1, n>, KERN<2, n>, KERN<3, n>, KERN<4, n>, KERN<5, n>, KERN<6, n>, KERN<7, n>, KERN<8, n>}
-template <int n>
-Kern forward_of(int m) {
-  static const Kern fwd[8] = CVD_V_ROW(viterbi_punct_forward_kernel);
-  return fwd[m - 1];
-}
-template <int n>
-Kern join_of(int m) {
-  static const Kern join[8] = CVD_V_ROW(viterbi_punct_join_kernel);
-  return join[m - 1];
-}
-#undef CVD_V_ROW
+CVD_VITERBI_PICK(viterbi_punct_forward_kernel, viterbi_punct_join_kernel)
 
 }  // namespace
 
@@ -210,43 +164,25 @@ extern "C" int cvd_viterbi_decode_punctured(const cvd_code* code, const uint8_t*
                                             const void* d_capture, int64_t nbits, int32_t format, int64_t start,
                                             int64_t T, int32_t block, int32_t warm, int32_t depth, uint32_t* d_bits,
                                             int64_t* d_stats, void* d_work, void* stream) {
-  if (!code || !code->taps) return invalid("null code");
-  if (code->k != 1 || code->n < 2 || code->n > 3 || code->m < 1 || code->m > 8) {
-    cvd::set_error(std::string(kWho) + ": needs k = 1, n in 2..3 and m in 1..8");
-    return CVD_E_UNSUPPORTED;
-  }
+  if (const int rc = cvd::viterbi_code_shape(kWho, code)) return rc;
   const int n = code->n, m = code->m;
-  if (!keep) return invalid("null keep");
-  if (period < 1 || period > 16) return invalid("period must be 1..16");
-  uint64_t pmask = 0, ppre[2] = {0, 0};
-  int32_t K = 0;
-  int pre[17];
-  for (int c = 0; c < period; ++c) {
-    if (keep[c] == 0) return invalid("a column of keep is zero: every step transmits at least one bit");
-    if (keep[c] >> n) return invalid("a column of keep has a bit at or above n");
-    pre[c] = K;
-    pmask |= (uint64_t)keep[c] << (4 * c);
-    ppre[c >> 3] |= (uint64_t)K << (8 * (c & 7));
-    K += __builtin_popcount(keep[c]);
-  }
-  pre[period] = K;
+  cvd::VPattern pat;
+  if (const int rc = cvd::viterbi_pack_pattern(kWho, "bit", keep, period, n, &pat)) return rc;
   // span = pos(T) - start; -1: an int64 overflow (T > 2^31 - 1 is reported as a bad T first)
   int64_t span = 0;
-  if (T > 0) {
-    if (__builtin_mul_overflow(T / period, (int64_t)K, &span) || __builtin_add_overflow(span, (int64_t)pre[T % period], &span))
-      span = -1;
-  }
+  if (T > 0 && !pat.span(T, &span)) span = -1;
   VArgs a;
   bool launch;
   const int rc = cvd::viterbi_setup(kWho, code, d_capture, nbits, format, start, T, span, block, warm, depth,
-                                    CVD_VITERBI_PUNCT_WARM(m, n, period, K), CVD_VITERBI_PUNCT_DEPTH(m, n, period, K),
-                                    d_bits, d_stats, d_work, &a, &launch);
+                                    CVD_VITERBI_PUNCT_WARM(m, n, period, pat.K),
+                                    CVD_VITERBI_PUNCT_DEPTH(m, n, period, pat.K), d_bits, d_stats, d_work, &a, &launch);
   if (rc != CVD_OK || !launch) return rc;
   a.period = period;
-  a.K = K;
-  a.pmask = pmask;
-  a.ppre[0] = ppre[0];
-  a.ppre[1] = ppre[1];
-  return cvd::viterbi_launch(m, a, n == 2 ? forward_of<2>(m) : forward_of<3>(m), n == 2 ? join_of<2>(m) : join_of<3>(m),
-                             stream);
+  a.K = pat.K;
+  a.pmask = pat.pmask;
+  a.ppre[0] = pat.ppre[0];
+  a.ppre[1] = pat.ppre[1];
+  Kern fwd, join;
+  pick(m, n, &fwd, &join);
+  return cvd::viterbi_launch(m, a, fwd, join, stream);
 }

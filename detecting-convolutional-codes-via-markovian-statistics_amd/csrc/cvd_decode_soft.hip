@@ -3,9 +3,11 @@
 // pass and the join know what a step's metric is made of; compare, look, trace and fix read
 // decision words and are cvd_decode.hip's (cvd::viterbi_launch with wide = true: the metric
 // vectors are 16-bit here, D <= 127 n m).  An erased bit is the value 0, so a punctured soft
-// capture is depunctured by a streaming kernel and decoded like any other.
+// capture is depunctured by a streaming kernel and decoded like any other.  The step loop and the
+// two kernels' bodies are cvd_decode_common.h's (acs_chunk, forward_body, join_body): SLane
+// overrides the four vector members and norm_of, and its run returns sum_t A_t.
 //
-// What differs from cvd_decode.hip's Lane::run:
+// What SLane brings where cvd_decode.hip's Lane has its funnel and 2-bit metric fields:
 //   metric    cost(out, t) = sum_j a(v_j) [v_j != 0 and (v_j > 0) != bit j of out], a(v) =
 //             min(|v|, 127).  With corr = sum_j (+-1 by bit j of out) v_j and A_t = sum_j a(v_j),
 //             2 cost = A_t - corr, and A_t is the same for every state: the loop carries
@@ -67,7 +69,8 @@ struct SLane : LaneBase<m> {
     }
   }
 
-  // 2 D as 16-bit D, and the byte min(D, 255) that look and fix test for zero
+  // The loop's x = 2 D - sum A_t; the vectors in memory are D, 16-bit, and the end vector also
+  // the byte min(D, 255) that look and fix test for zero.
   __device__ __forceinline__ void store16(uint16_t* vec, uint8_t* bytes, const int (&X)[SPL]) const {
     if (lane < S) {
 #pragma unroll
@@ -78,15 +81,33 @@ struct SLane : LaneBase<m> {
       }
     }
   }
+  __device__ __forceinline__ void store_warm(const VArgs& a, int64_t b, const int (&X)[SPL]) const {
+    store16(a.warm16 + b * S, nullptr, X);
+  }
+  __device__ __forceinline__ void store_end(const VArgs& a, int64_t b, const int (&X)[SPL]) const {
+    store16(a.end16 + b * S, a.endv + b * S, X);
+  }
+  __device__ __forceinline__ void load_end(const VArgs& a, int64_t b, int (&X)[SPL]) const {
+#pragma unroll
+    for (int i = 0; i < SPL; ++i) X[i] = 2 * (int)a.end16[b * S + state(i)];
+  }
+  __device__ __forceinline__ bool differs_from_warm(const VArgs& a, int64_t b, const int (&X)[SPL]) const {
+    bool diff = false;
+#pragma unroll
+    for (int i = 0; i < SPL; ++i) diff |= X[i] != 2 * (int)a.warm16[b * S + state(i)];
+    return diff;
+  }
+  __device__ __forceinline__ static int norm_of(int mn, int asum) { return (mn + asum) >> 1; }
+
+  // vs: a step's n values, packed
+  __device__ __forceinline__ int cand0(int i, int vs, int x) const { return __builtin_amdgcn_sdot4(pat0[i], vs, x, false); }
+  __device__ __forceinline__ int cand1(int i, int vs, int x) const { return __builtin_amdgcn_sdot4(pat1[i], vs, x, false); }
 
   // steps [t0, t1) on x (not normalised); record as in cvd_decode.hip's Lane::run.  Returns the
   // sum of A_t over the steps.  LDS: st kSoftStageU4 pieces, met 2 S ints (S > 64).
   template <bool record>
   __device__ __forceinline__ int run(const VArgs& a, int64_t t0, int64_t t1, int (&X)[SPL], uint64_t* dec, uint4* st,
                                      int* met) const {
-    uint32_t mlo[SPL], mhi[SPL];                         // lane j: the decision word of the chunk's step j
-#pragma unroll
-    for (int i = 0; i < SPL; ++i) mlo[i] = mhi[i] = 0u;
     int cur = 0;
     int asum = 0;                                        // this lane's share of sum A_t
     const int8_t* sb = reinterpret_cast<const int8_t*>(st);
@@ -115,114 +136,34 @@ struct SLane : LaneBase<m> {
             vp |= (v & 255) << (8 * j);
           }
         }
-        for (int jj = 0; jj < c64; ++jj) {
-          const int vs = __builtin_amdgcn_readlane(vp, jj);
-          if constexpr (SPL > 1) {
-#pragma unroll
-            for (int i = 0; i < SPL; ++i) met[cur * S + state(i)] = X[i];
-            __syncthreads();
-          }
-#pragma unroll
-          for (int i = 0; i < SPL; ++i) {
-            int a0, a1;
-            if constexpr (SPL > 1) {
-              a0 = met[cur * S + ps0[i]];
-              a1 = met[cur * S + ps1[i]];
-            } else {
-              a0 = __shfl(X[0], ps0[0]);
-              a1 = __shfl(X[0], ps1[0]);
-            }
-            const int x0 = __builtin_amdgcn_sdot4(pat0[i], vs, a0, false);
-            const int x1 = __builtin_amdgcn_sdot4(pat1[i], vs, a1, false);
-            bool d = x1 < x0;                            // ties keep b = 0
-            X[i] = min(x0, x1);
-            if constexpr (record) {
-              if constexpr (S < kWave) d = d && lane < S;
-              const uint64_t bal = __builtin_amdgcn_ballot_w64(d);
-              if (lane == jj) {
-                mlo[i] = (uint32_t)bal;
-                mhi[i] = (uint32_t)(bal >> 32);
-              }
-            }
-          }
-          cur ^= 1;
-        }
-        if constexpr (record) {
-          if (lane < c64) {
-            uint64_t* p = dec + ((seg - t0) + j0 + lane) * SPL;
-#pragma unroll
-            for (int i = 0; i < SPL; ++i) p[i] = ((uint64_t)mhi[i] << 32) | mlo[i];
-          }
-        }
+        acs_chunk<record>(*this, c64, X, cur, met, dec + ((seg - t0) + j0) * SPL,
+                          [&](int jj) { return __builtin_amdgcn_readlane(vp, jj); });
       }
     }
 #pragma unroll
     for (int k = 1; k < kWave; k <<= 1) asum += __shfl_xor(asum, k);
     return asum;
   }
-
-  // block b's steps from x = 2 D: decisions, end vector and normalisation
-  __device__ __forceinline__ void block(const VArgs& a, int64_t b, int (&X)[SPL], uint4* st, int* met) const {
-    const int64_t lo = b * a.L, hi = min(a.T, lo + a.L);
-    const int asum = this->template run<true>(a, lo, hi, X, a.dec + lo * SPL, st, met);
-    const int mn = this->normalise(X);
-    store16(a.end16 + b * S, a.endv + b * S, X);
-    if (lane == 0) a.norm[b] = (mn + asum) >> 1;
-  }
 };
 
-// cvd_decode_common.h's forward_body and join_body over 16-bit vectors and the doubled metric
 template <int m, int n>
 __global__ __launch_bounds__(kWave) void viterbi_soft_forward_kernel(VArgs a) {
   using Sh = Shape<m>;
-  constexpr int S = Sh::S, SPL = Sh::SPL;
   __shared__ uint4 st[kSoftStageU4];
-  __shared__ int met[SPL > 1 ? 2 * S : 1];
+  __shared__ int met[Sh::SPL > 1 ? 2 * Sh::S : 1];
   SLane<m, n> ln;
   ln.init(a);
-  const int64_t b = blockIdx.x;
-  const int64_t lo = b * a.L, t0 = max((int64_t)0, lo - a.W);
-  int X[SPL];
-#pragma unroll
-  for (int i = 0; i < SPL; ++i) X[i] = 0;
-  if (t0 < lo) {
-    ln.template run<false>(a, t0, lo, X, nullptr, st, met);
-    ln.normalise(X);
-  }
-  ln.store16(a.warm16 + b * S, nullptr, X);
-  ln.block(a, b, X, st, met);
+  forward_body(a, ln, st, met);
 }
 
 template <int m, int n>
 __global__ __launch_bounds__(kWave) void viterbi_soft_join_kernel(VArgs a) {
   using Sh = Shape<m>;
-  constexpr int S = Sh::S, SPL = Sh::SPL;
   __shared__ uint4 st[kSoftStageU4];
-  __shared__ int met[SPL > 1 ? 2 * S : 1];
+  __shared__ int met[Sh::SPL > 1 ? 2 * Sh::S : 1];
   SLane<m, n> ln;
   ln.init(a);
-  int X[SPL];
-  unsigned long long reruns = 0;
-  int64_t b = 1;
-  while (b < a.nb) {
-    const int64_t idx = b + ln.lane;
-    const uint64_t bal = __ballot(idx < a.nb && a.mis[idx] != 0);
-    if (!bal) { b += kWave; continue; }
-    b += __builtin_ctzll(bal);
-#pragma unroll
-    for (int i = 0; i < SPL; ++i) X[i] = 2 * (int)a.end16[(b - 1) * S + ln.state(i)];   // block b - 1 stands
-    while (b < a.nb) {
-      bool diff = false;
-#pragma unroll
-      for (int i = 0; i < SPL; ++i) diff |= X[i] != 2 * (int)a.warm16[b * S + ln.state(i)];
-      if (!__any(diff)) break;
-      ++reruns;
-      ln.block(a, b, X, st, met);
-      ++b;
-    }
-    ++b;                                                 // block b joined: scan on behind it
-  }
-  if (ln.lane == 0) a.cnt[1] = reruns;
+  join_body(a, ln, st, met);
 }
 
 // stats[9], stats[10] (zeroed before the launch): a thread per step re-encodes the step from
@@ -305,59 +246,18 @@ __global__ __launch_bounds__(256) void soft_depuncture_kernel(DArgs a) {
   a.out[i] = word;
 }
 
-#define HIP_CHECK(x)                                                                      \
-  do {                                                                                    \
-    hipError_t e_ = (x);                                                                  \
-    if (e_ != hipSuccess) {                                                               \
-      cvd::set_error(std::string("HIP error '") + hipGetErrorString(e_) + "' at " #x);     \
-      return CVD_E_HIP;                                                                   \
-    }                                                                                     \
-  } while (0)
-
-int invalid(const char* who, const char* what) {
-  cvd::set_error(std::string(who) + ": " + what);
-  return CVD_E_INVALID;
-}
-
-int64_t round16(int64_t x) { return (x + 15) / 16 * 16; }
-
-using Kern = void (*)(VArgs);
-#define CVD_V_ROW(KERN) {KERN<1, n>, KERN<2, n>, KERN<3, n>, KERN<4, n>, KERN<5, n>, KERN<6, n>, KERN<7, n>, KERN<8, n>}
-template <int n>
-Kern forward_of(int m) {
-  static const Kern fwd[8] = CVD_V_ROW(viterbi_soft_forward_kernel);
-  return fwd[m - 1];
-}
-template <int n>
-Kern join_of(int m) {
-  static const Kern join[8] = CVD_V_ROW(viterbi_soft_join_kernel);
-  return join[m - 1];
-}
-#undef CVD_V_ROW
+CVD_VITERBI_PICK(viterbi_soft_forward_kernel, viterbi_soft_join_kernel)
 
 }  // namespace
 
-// cvd_viterbi_decode's workspace, then the two arrays of 16-bit vectors
 extern "C" int64_t cvd_viterbi_soft_workspace_bytes(int32_t n, int32_t m, int64_t T, int32_t block) {
-  const int64_t base = cvd_viterbi_workspace_bytes(n, m, T, block);
-  if (base < 0) {
-    const std::string why = cvd::last_error_copy();      // "viterbi_decode: ..."
-    const size_t at = why.find(": ");
-    cvd::set_error(std::string(kWho) + (at == std::string::npos ? ": " + why : why.substr(at)));
-    return base;
-  }
-  const int64_t L = block ? block : CVD_VITERBI_BLOCK, nb = ((T > 0 ? T : 1) + L - 1) / L;
-  return base + 2 * round16(nb * ((int64_t)2 << m));
+  return cvd::viterbi_workspace_bytes(kWho, n, m, T, block, true);
 }
 
 extern "C" int cvd_viterbi_decode_soft(const cvd_code* code, const int8_t* d_soft, int64_t nvals, int64_t start,
                                        int64_t T, int32_t block, int32_t warm, int32_t depth, uint32_t* d_bits,
                                        int64_t* d_stats, void* d_work, void* stream) {
-  if (!code || !code->taps) return invalid(kWho, "null code");
-  if (code->k != 1 || code->n < 2 || code->n > 3 || code->m < 1 || code->m > 8) {
-    cvd::set_error(std::string(kWho) + ": needs k = 1, n in 2..3 and m in 1..8");
-    return CVD_E_UNSUPPORTED;
-  }
+  if (const int rc = cvd::viterbi_code_shape(kWho, code)) return rc;
   const int n = code->n, m = code->m;
   int64_t span;
   if (T >= 0 && __builtin_mul_overflow(T, (int64_t)n, &span)) span = -1;
@@ -371,14 +271,11 @@ extern "C" int cvd_viterbi_decode_soft(const cvd_code* code, const int8_t* d_sof
   bool launch;
   // one value per byte: the capture checks are those of a CVD_CAPTURE_BYTES capture of nvals bytes
   const int rc = cvd::viterbi_setup(kWho, code, d_soft, nvals, CVD_CAPTURE_BYTES, start, T, span, block, warm, depth,
-                                    CVD_VITERBI_WARM(m), CVD_VITERBI_DEPTH(m), d_bits, d_stats, d_work, &a, &launch);
+                                    CVD_VITERBI_WARM(m), CVD_VITERBI_DEPTH(m), d_bits, d_stats, d_work, &a, &launch, true);
   if (rc != CVD_OK || !launch) return rc;
-  const int64_t vec = round16(a.nb * ((int64_t)2 << m));
-  char* w = static_cast<char*>(d_work) + cvd_viterbi_workspace_bytes(n, m, T, a.L);
-  a.warm16 = reinterpret_cast<uint16_t*>(w);
-  a.end16 = reinterpret_cast<uint16_t*>(w + vec);
-  const int lrc = cvd::viterbi_launch(m, a, n == 2 ? forward_of<2>(m) : forward_of<3>(m),
-                                      n == 2 ? join_of<2>(m) : join_of<3>(m), stream, true);
+  Kern fwd, join;
+  pick(m, n, &fwd, &join);
+  const int lrc = cvd::viterbi_launch(m, a, fwd, join, stream, true);
   if (lrc != CVD_OK) return lrc;
   hipStream_t st = (hipStream_t)stream;
   HIP_CHECK(hipMemsetAsync(d_stats + 9, 0, 16, st));
@@ -392,28 +289,21 @@ extern "C" int cvd_viterbi_decode_soft(const cvd_code* code, const int8_t* d_sof
 extern "C" int cvd_soft_depuncture(const int8_t* d_in, int64_t nvals, int64_t start, const uint8_t* keep,
                                    int32_t period, int32_t n, int64_t T, int8_t* d_out, void* stream) {
   if (n < 2 || n > 3) return invalid(kWhoDep, "needs n in 2..3");
-  if (!keep) return invalid(kWhoDep, "null keep");
-  if (period < 1 || period > 16) return invalid(kWhoDep, "period must be 1..16");
-  DArgs a{};
-  int pre[17];
-  for (int c = 0; c < period; ++c) {
-    if (keep[c] == 0) return invalid(kWhoDep, "a column of keep is zero: every step transmits at least one value");
-    if (keep[c] >> n) return invalid(kWhoDep, "a column of keep has a bit at or above n");
-    pre[c] = a.K;
-    a.pmask |= (uint64_t)keep[c] << (4 * c);
-    a.ppre[c >> 3] |= (uint64_t)a.K << (8 * (c & 7));
-    a.K += __builtin_popcount(keep[c]);
-  }
-  pre[period] = a.K;
+  cvd::VPattern pat;
+  if (const int rc = cvd::viterbi_pack_pattern(kWhoDep, "value", keep, period, n, &pat)) return rc;
   if (T < 0 || T > INT32_MAX) return invalid(kWhoDep, "T must be 0..2^31 - 1");
   if (start < 0 || nvals < 0) return invalid(kWhoDep, "needs start, nvals >= 0");
   int64_t span = 0, end;
-  if (__builtin_mul_overflow(T / period, (int64_t)a.K, &span) ||
-      __builtin_add_overflow(span, (int64_t)pre[T % period], &span) || __builtin_add_overflow(span, start, &end))
+  if (!pat.span(T, &span) || __builtin_add_overflow(span, start, &end))
     return invalid(kWhoDep, "the position of the last value's end overflows int64");
   if (end > nvals) return invalid(kWhoDep, "the values do not lie inside [0, nvals)");
   if (T == 0) return CVD_OK;
   if (!d_in || !d_out || ((uintptr_t)d_out & 15)) return invalid(kWhoDep, "d_in and d_out (16-byte aligned) must be non-null");
+  DArgs a{};
+  a.K = pat.K;
+  a.pmask = pat.pmask;
+  a.ppre[0] = pat.ppre[0];
+  a.ppre[1] = pat.ppre[1];
   a.total = (int64_t)n * T;
   const int64_t nout = round16(a.total);
   const uintptr_t i0 = (uintptr_t)d_in, o0 = (uintptr_t)d_out;

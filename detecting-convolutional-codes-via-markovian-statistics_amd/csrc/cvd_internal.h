@@ -234,14 +234,34 @@ int device_learn_dense(const CodeDesc& dec, const std::vector<int32_t>& next, in
 namespace vit {
 struct VArgs;   // cvd_decode_common.h
 }
+// The three entry points' first check: a k = 1 code with n in 2..3 and m in 1..8, else the error
+// naming `who`.
+int viterbi_code_shape(const char* who, const struct ::cvd_code* code);
+// A puncturing pattern as the kernels read it (VArgs' fields of these names).  span: pos(T) -
+// start for T >= 0, false on an int64 overflow.
+struct VPattern {
+  uint64_t pmask = 0, ppre[2] = {0, 0};
+  int32_t period = 0, K = 0;
+  int pre[17];
+  bool span(int64_t T, int64_t* out) const {
+    return !__builtin_mul_overflow(T / period, (int64_t)K, out) && !__builtin_add_overflow(*out, (int64_t)pre[T % period], out);
+  }
+};
+// Checks keep (non-null, period 1..16, every column nonzero and below 2^n) and packs it; the
+// errors name `who` and call what a step transmits `noun` ("bit", "value").
+int viterbi_pack_pattern(const char* who, const char* noun, const uint8_t* keep, int32_t period, int32_t n, VPattern* out);
+// cvd_viterbi_workspace_bytes (wide: cvd_viterbi_soft_workspace_bytes, the two arrays of 16-bit
+// vectors behind it), the errors naming `who`.
+int64_t viterbi_workspace_bytes(const char* who, int32_t n, int32_t m, int64_t T, int32_t block, bool wide);
 // cvd_viterbi_decode's argument checks behind the code shape and the workspace layout, with the
 // errors naming `who`: the T steps read `span` capture bits from `start` (-1: an int64 overflow
 // on the way to it), warm / depth -1 resolve to warm_default / depth_default.  CVD_OK with
-// *launch = false at T == 0, else `a` is filled in (the pattern fields zero).
+// *launch = false at T == 0, else `a` is filled in (the pattern fields zero; wide: with the
+// 16-bit vectors' places).
 int viterbi_setup(const char* who, const struct ::cvd_code* code, const void* d_capture, int64_t nbits, int32_t format,
                   int64_t start, int64_t T, int64_t span, int32_t block, int32_t warm, int32_t depth,
                   int32_t warm_default, int32_t depth_default, uint32_t* d_bits, int64_t* d_stats, void* d_work,
-                  vit::VArgs* a, bool* launch);
+                  vit::VArgs* a, bool* launch, bool wide = false);
 // memset, fwd (one wave per block), compare, join (one wave), look, trace, fix on `stream`.
 // wide: fwd and join keep 16-bit vectors in a.warm16 / a.end16 (cvd_decode_soft.hip), and the
 // compare step goes over their 2 * 2^m bytes.

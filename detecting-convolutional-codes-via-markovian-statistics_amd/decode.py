@@ -43,6 +43,67 @@ def default_depth(m):
     return 24 * (int(m) + 2)
 
 
+def _steps(T, block, warm, depth):
+    """T, block, warm and depth as the library takes them: 0 / -1 ask for its defaults."""
+    T = int(T)
+    if T < 0:
+        raise ValueError("T must be >= 0")
+    if T > MAX_T:
+        raise ValueError(f"T = {T}: one call decodes at most 2^31 - 1 steps")
+    blk = 0 if block is None else int(block)
+    wrm = -1 if warm is None else int(warm)
+    dep = -1 if depth is None else int(depth)
+    if (block is not None and blk <= 0) or (warm is not None and wrm < 0) or (depth is not None and dep < 0):
+        raise ValueError("needs block > 0 (a multiple of 32), warm >= 0 and depth >= 0")
+    return T, blk, wrm, dep
+
+
+def _decode(who, entry, workspace, lead, fmt, cap, nbits, start, n, m, T, blk, wrm, dep, nstats, warm0, depth0, dev,
+            prepare=None):
+    """One call of the library's decoder `entry`(*lead, capture, nbits, *fmt, start, T, block, warm,
+    depth, bits, stats, work, stream) over T steps: (bits, the nstats stats as a list).  T == 0
+    launches nothing: the call validates, and the stats report block, warm and depth as resolved
+    (warm0 / depth0: the defaults).  prepare(lib) -> (cap, nbits, start), if given, runs behind
+    the shape check.  `workspace` is the entry point that sizes d_work, `who` names the caller
+    in the MemoryError."""
+    L = _lib.lib()
+    call = getattr(L, entry)
+    wbytes = int(getattr(L, workspace)(n, m, T, blk))
+    if wbytes < 0:
+        # the decoder itself names an unsupported code shape
+        _lib.check(call(*lead, None, 0, *fmt, 0, 0, blk, wrm, dep, None, None, None, None))
+        _lib.check(wbytes)
+    with torch.cuda.device(dev):
+        bits = torch.zeros((T + 31) // 32 * 4, dtype=torch.uint8, device=dev)
+        stats = torch.zeros(nstats, dtype=torch.int64, device=dev)
+        if prepare is not None:
+            cap, nbits, start = prepare(L)
+        if T == 0:
+            # no launch: validate the arguments, report the resolved defaults
+            _lib.check(call(*lead, ctypes.c_void_p(cap.data_ptr()), nbits, *fmt, start, 0, blk, wrm, dep, None, None,
+                            None, _stream_ptr()))
+            s = [0, 0, 0, 0, 0, 0, blk or DEFAULT_BLOCK, warm0 if wrm < 0 else wrm, depth0 if dep < 0 else dep]
+            s += [0] * (nstats - len(s))
+        else:
+            free = torch.cuda.mem_get_info(dev)[0]
+            if wbytes > free:
+                raise MemoryError(f"{who}: the workspace of T = {T} steps (m = {m}) is {wbytes} bytes, "
+                                  f"{free} bytes of device memory are free: decode the capture in pieces")
+            work = torch.empty(wbytes, dtype=torch.uint8, device=dev)
+            _lib.check(call(*lead, ctypes.c_void_p(cap.data_ptr()), nbits, *fmt, start, T, blk, wrm, dep,
+                            ctypes.c_void_p(bits.data_ptr()), ctypes.c_void_p(stats.data_ptr()),
+                            ctypes.c_void_p(work.data_ptr()), _stream_ptr()))
+            s = stats.cpu().tolist()     # synchronises: cap and work may be freed on return
+    return bits, s
+
+
+def _result(bits, T, s, errors, ber):
+    """decode_capture's dict from the stats."""
+    return {"bits": bits, "T": T, "errors": int(errors), "ber": ber,
+            "start_state": int(s[4]), "end_state": int(s[5]), "blocks": int(s[1]), "forward_reruns": int(s[2]),
+            "trace_fixups": int(s[3]), "block": int(s[6]), "warm": int(s[7]), "depth": int(s[8])}
+
+
 def decode_capture(n, m, gen, capture, start=0, T=None, format="bytes", nbits=None, block=None, warm=None,
                    depth=None, device=None):
     """cvd_viterbi_decode over a capture (numpy array or torch tensor of uint8, as
@@ -59,44 +120,10 @@ def decode_capture(n, m, gen, capture, start=0, T=None, format="bytes", nbits=No
     cap, fmt, nbits = capture_buffer(capture, format, nbits, dev)
     if T is None:
         T = max(0, nbits - start) // n if start >= 0 else 0
-    T = int(T)
-    if T < 0:
-        raise ValueError("T must be >= 0")
-    if T > MAX_T:
-        raise ValueError(f"T = {T}: one call decodes at most 2^31 - 1 steps")
-    blk = 0 if block is None else int(block)
-    wrm = -1 if warm is None else int(warm)
-    dep = -1 if depth is None else int(depth)
-    if (block is not None and blk <= 0) or (warm is not None and wrm < 0) or (depth is not None and dep < 0):
-        raise ValueError("needs block > 0 (a multiple of 32), warm >= 0 and depth >= 0")
-    L = _lib.lib()
-    wbytes = int(L.cvd_viterbi_workspace_bytes(n, m, T, blk))
-    if wbytes < 0:
-        # the decoder itself names an unsupported code shape
-        _lib.check(L.cvd_viterbi_decode(code.c, None, 0, fmt, 0, 0, blk, wrm, dep, None, None, None, None))
-        _lib.check(wbytes)
-    with torch.cuda.device(dev):
-        bits = torch.zeros((T + 31) // 32 * 4, dtype=torch.uint8, device=dev)
-        stats = torch.zeros(9, dtype=torch.int64, device=dev)
-        if T == 0:
-            # no launch: validate the arguments, report the resolved defaults
-            _lib.check(L.cvd_viterbi_decode(code.c, ctypes.c_void_p(cap.data_ptr()), nbits, fmt, start, 0, blk, wrm,
-                                            dep, None, None, None, _stream_ptr()))
-            s = [0, 0, 0, 0, 0, 0, blk or DEFAULT_BLOCK, default_warm(m) if wrm < 0 else wrm,
-                 default_depth(m) if dep < 0 else dep]
-        else:
-            free = torch.cuda.mem_get_info(dev)[0]
-            if wbytes > free:
-                raise MemoryError(f"decode_capture: the workspace of T = {T} steps (m = {m}) is {wbytes} bytes, "
-                                  f"{free} bytes of device memory are free: decode the capture in pieces")
-            work = torch.empty(wbytes, dtype=torch.uint8, device=dev)
-            _lib.check(L.cvd_viterbi_decode(code.c, ctypes.c_void_p(cap.data_ptr()), nbits, fmt, start, T, blk, wrm,
-                                            dep, ctypes.c_void_p(bits.data_ptr()), ctypes.c_void_p(stats.data_ptr()),
-                                            ctypes.c_void_p(work.data_ptr()), _stream_ptr()))
-            s = stats.cpu().tolist()     # synchronises: cap and work may be freed on return
-    return {"bits": bits, "T": T, "errors": int(s[0]), "ber": s[0] / (n * T) if T else 0.0,
-            "start_state": int(s[4]), "end_state": int(s[5]), "blocks": int(s[1]), "forward_reruns": int(s[2]),
-            "trace_fixups": int(s[3]), "block": int(s[6]), "warm": int(s[7]), "depth": int(s[8])}
+    T, blk, wrm, dep = _steps(T, block, warm, depth)
+    bits, s = _decode("decode_capture", "cvd_viterbi_decode", "cvd_viterbi_workspace_bytes", (code.c,), (fmt,), cap,
+                      nbits, start, n, m, T, blk, wrm, dep, 9, default_warm(m), default_depth(m), dev)
+    return _result(bits, T, s, s[0], s[0] / (n * T) if T else 0.0)
 
 
 # ───────────────────────────── punctured captures ───────────────────────────
@@ -183,49 +210,13 @@ def decode_capture_punctured(n, m, gen, keep, capture, start=0, T=None, format="
     cap, fmt, nbits = capture_buffer(capture, format, nbits, dev)
     if T is None:
         T = punctured_steps(nbits - start, keep) if start >= 0 else 0
-    T = int(T)
-    if T < 0:
-        raise ValueError("T must be >= 0")
-    if T > MAX_T:
-        raise ValueError(f"T = {T}: one call decodes at most 2^31 - 1 steps")
-    blk = 0 if block is None else int(block)
-    wrm = -1 if warm is None else int(warm)
-    dep = -1 if depth is None else int(depth)
-    if (block is not None and blk <= 0) or (warm is not None and wrm < 0) or (depth is not None and dep < 0):
-        raise ValueError("needs block > 0 (a multiple of 32), warm >= 0 and depth >= 0")
-    L = _lib.lib()
-    kbytes = bytes(keep)
-    wbytes = int(L.cvd_viterbi_workspace_bytes(n, m, T, blk))
-    if wbytes < 0:
-        # the decoder itself names an unsupported code shape
-        _lib.check(L.cvd_viterbi_decode_punctured(code.c, kbytes, period, None, 0, fmt, 0, 0, blk, wrm, dep, None,
-                                                  None, None, None))
-        _lib.check(wbytes)
-    with torch.cuda.device(dev):
-        bits = torch.zeros((T + 31) // 32 * 4, dtype=torch.uint8, device=dev)
-        stats = torch.zeros(10, dtype=torch.int64, device=dev)
-        if T == 0:
-            # no launch: validate the arguments, report the resolved defaults
-            _lib.check(L.cvd_viterbi_decode_punctured(code.c, kbytes, period, ctypes.c_void_p(cap.data_ptr()), nbits,
-                                                      fmt, start, 0, blk, wrm, dep, None, None, None, _stream_ptr()))
-            s = [0, 0, 0, 0, 0, 0, blk or DEFAULT_BLOCK,
-                 default_warm_punctured(m, n, period, K) if wrm < 0 else wrm,
-                 default_depth_punctured(m, n, period, K) if dep < 0 else dep, 0]
-        else:
-            free = torch.cuda.mem_get_info(dev)[0]
-            if wbytes > free:
-                raise MemoryError(f"decode_capture_punctured: the workspace of T = {T} steps (m = {m}) is {wbytes} "
-                                  f"bytes, {free} bytes of device memory are free: decode the capture in pieces")
-            work = torch.empty(wbytes, dtype=torch.uint8, device=dev)
-            _lib.check(L.cvd_viterbi_decode_punctured(code.c, kbytes, period, ctypes.c_void_p(cap.data_ptr()), nbits,
-                                                      fmt, start, T, blk, wrm, dep, ctypes.c_void_p(bits.data_ptr()),
-                                                      ctypes.c_void_p(stats.data_ptr()),
-                                                      ctypes.c_void_p(work.data_ptr()), _stream_ptr()))
-            s = stats.cpu().tolist()     # synchronises: cap and work may be freed on return
-    return {"bits": bits, "T": T, "errors": int(s[0]), "ber": s[0] / s[9] if T else 0.0,
-            "start_state": int(s[4]), "end_state": int(s[5]), "blocks": int(s[1]), "forward_reruns": int(s[2]),
-            "trace_fixups": int(s[3]), "block": int(s[6]), "warm": int(s[7]), "depth": int(s[8]),
-            "capture_bits": int(s[9])}
+    T, blk, wrm, dep = _steps(T, block, warm, depth)
+    bits, s = _decode("decode_capture_punctured", "cvd_viterbi_decode_punctured", "cvd_viterbi_workspace_bytes",
+                      (code.c, bytes(keep), period), (fmt,), cap, nbits, start, n, m, T, blk, wrm, dep, 10,
+                      default_warm_punctured(m, n, period, K), default_depth_punctured(m, n, period, K), dev)
+    res = _result(bits, T, s, s[0], s[0] / s[9] if T else 0.0)
+    res["capture_bits"] = int(s[9])
+    return res
 
 
 def sync_punctured(n, m, gen, keep, capture, start=0, T=1000, format="bytes", nbits=None, block=None, warm=None,
@@ -331,55 +322,20 @@ def decode_capture_soft(n, m, gen, soft, start=0, T=None, keep=None, block=None,
     if T is None:
         fit = max(0, nvals - start) if start >= 0 else 0
         T = fit // n if keep is None else punctured_steps(fit, keep)
-    T = int(T)
-    if T < 0:
-        raise ValueError("T must be >= 0")
-    if T > MAX_T:
-        raise ValueError(f"T = {T}: one call decodes at most 2^31 - 1 steps")
-    blk = 0 if block is None else int(block)
-    wrm = -1 if warm is None else int(warm)
-    dep = -1 if depth is None else int(depth)
-    if (block is not None and blk <= 0) or (warm is not None and wrm < 0) or (depth is not None and dep < 0):
-        raise ValueError("needs block > 0 (a multiple of 32), warm >= 0 and depth >= 0")
+    T, blk, wrm, dep = _steps(T, block, warm, depth)
+    prepare = None
     if keep is not None:
         period, K = len(keep), punctured_bits(len(keep), keep)
         if wrm < 0:
             wrm = default_warm_punctured(m, n, period, K)
         if dep < 0:
             dep = default_depth_punctured(m, n, period, K)
-    L = _lib.lib()
-    wbytes = int(L.cvd_viterbi_soft_workspace_bytes(n, m, T, blk))
-    if wbytes < 0:
-        # the decoder itself names an unsupported code shape
-        _lib.check(L.cvd_viterbi_decode_soft(code.c, None, 0, 0, 0, blk, wrm, dep, None, None, None, None))
-        _lib.check(wbytes)
-    with torch.cuda.device(dev):
-        bits = torch.zeros((T + 31) // 32 * 4, dtype=torch.uint8, device=dev)
-        stats = torch.zeros(11, dtype=torch.int64, device=dev)
-        if keep is not None:
-            # validates the pattern's range; T == 0: no launch
-            cap, nvals, start = _depuncture(L, cap, nvals, start, keep, n, T, dev), n * T, 0
-        if T == 0:
-            # no launch: validate the arguments, report the resolved defaults
-            _lib.check(L.cvd_viterbi_decode_soft(code.c, ctypes.c_void_p(cap.data_ptr()), nvals, start, 0, blk, wrm,
-                                                 dep, None, None, None, _stream_ptr()))
-            s = [0, 0, 0, 0, 0, 0, blk or DEFAULT_BLOCK, default_warm(m) if wrm < 0 else wrm,
-                 default_depth(m) if dep < 0 else dep, 0, 0]
-        else:
-            free = torch.cuda.mem_get_info(dev)[0]
-            if wbytes > free:
-                raise MemoryError(f"decode_capture_soft: the workspace of T = {T} steps (m = {m}) is {wbytes} bytes, "
-                                  f"{free} bytes of device memory are free: decode the capture in pieces")
-            work = torch.empty(wbytes, dtype=torch.uint8, device=dev)
-            _lib.check(L.cvd_viterbi_decode_soft(code.c, ctypes.c_void_p(cap.data_ptr()), nvals, start, T, blk, wrm,
-                                                 dep, ctypes.c_void_p(bits.data_ptr()),
-                                                 ctypes.c_void_p(stats.data_ptr()), ctypes.c_void_p(work.data_ptr()),
-                                                 _stream_ptr()))
-            s = stats.cpu().tolist()     # synchronises: cap and work may be freed on return
-    res = {"bits": bits, "T": T, "errors": int(s[9]), "ber": s[9] / s[10] if s[10] else 0.0,
-           "start_state": int(s[4]), "end_state": int(s[5]), "blocks": int(s[1]), "forward_reruns": int(s[2]),
-           "trace_fixups": int(s[3]), "block": int(s[6]), "warm": int(s[7]), "depth": int(s[8]),
-           "metric": int(s[0]), "erasures": n * T - int(s[10])}
+        # validates the pattern's range; T == 0: no launch
+        prepare = lambda L: (_depuncture(L, cap, nvals, start, keep, n, T, dev), n * T, 0)
+    bits, s = _decode("decode_capture_soft", "cvd_viterbi_decode_soft", "cvd_viterbi_soft_workspace_bytes", (code.c,), (),
+                      cap, nvals, start, n, m, T, blk, wrm, dep, 11, default_warm(m), default_depth(m), dev, prepare)
+    res = _result(bits, T, s, s[9], s[9] / s[10] if s[10] else 0.0)
+    res.update(metric=int(s[0]), erasures=n * T - int(s[10]))
     if keep is not None:
         res["capture_bits"] = punctured_bits(T, keep)
     return res
