@@ -35,6 +35,8 @@
       takes it.  Single-process, like scan.
   ... decode --code C --input FILE [--format bytes|lsb|msb|soft] [--nbits B] [--start S] [--T T]
              [--out-bits FILE.npy] [--puncture SPEC [--sync T0]]
+             [--frame T [--frame-count F] [--frame-stride B | --frame-offsets FILE.npy]
+              [--start-state S|any] [--end-state S|any]]
       (nothing in the reference) -- what was sent: the hard-decision Viterbi decoder of the
       k = 1 code C over the capture from bit S (cvd_viterbi_decode: the Eq. 4-5 recursion with
       its survivor decisions kept, exact whatever the block split); writes the decoded bits to
@@ -55,6 +57,17 @@
       The CSV gains metric (the soft distance of the decoded path) and erasures; errors
       counts the values whose sign disagrees with the path, ber = errors / non-erased values.
       No scan line is printed: the detector's model is a BSC model.
+      --frame T: the capture holds frames of T steps each (802.11a/g PPDUs, GSM bursts, packets),
+      decoded in one call (cvd_viterbi_decode_frames and its punctured and soft siblings): frame
+      f begins at bit S + f*B (--frame-stride B; default: the frames follow one another), or at
+      the int64 offsets of --frame-offsets (a frame that does not lie inside the capture is
+      skipped); --frame-count F frames (default: as many as fit).  --start-state / --end-state:
+      the encoder's state before / after a frame, or any; the defaults, 0 and 0, are terminated
+      frames.  Works with --puncture (the pattern restarts in every frame) and --format soft (not
+      both); an error together with --T or --sync.  Writes <save-dir>/decoded.npy (uint8 [F, 4w],
+      w = ceil(T/32): a row per frame, LSB-first) and <save-dir>/decode_frames.csv, a row per
+      frame: frame, offset, status (0 decoded, 1 skipped), distance, errors, counted,
+      start_state, end_state; prints the totals and p = errors / counted.
 
 Codes: the BASELINE configurations (m2, m6, r23_m4), the demo presets (example:1,
 example:2, demo_script.py:35-52), or oct:G0,G1[,G2] -- k = 1 generators in octal (MSB =
@@ -71,9 +84,10 @@ import re
 import sys
 
 from . import (CONFIG_CODES, DEFAULTS, EXAMPLE_CODES, compute_error_exponent, default_template,
-               decode_capture, decode_capture_punctured, decode_capture_soft, find_parity_checks,
+               decode_capture, decode_capture_punctured, decode_capture_soft, decode_frames, decode_frames_soft,
+               find_parity_checks,
                learn_transition_tensor, octal_to_taps, parity_experiment, parity_vector_to_equation, parity_vectors,
-               puncture_pattern, run_experiment, scan_capture, sync_punctured, sync_punctured_soft)
+               puncture_pattern, punctured_bits, run_experiment, scan_capture, sync_punctured, sync_punctured_soft)
 
 PROG = "python -m detecting-convolutional-codes-via-markovian-statistics_amd"
 
@@ -201,12 +215,55 @@ def parser():
     d.add_argument("--sync", type=int, default=None, metavar="T0",
                    help="with --puncture: try the K bit offsets of a period over the first T0 steps from --start "
                         "and decode from the best")
+    d.add_argument("--frame", type=int, default=None, metavar="T",
+                   help="the capture holds frames of T steps each, decoded in one call (not with --T or --sync)")
+    d.add_argument("--frame-count", type=int, default=None, metavar="F", help="frames (default: as many as fit)")
+    d.add_argument("--frame-stride", type=int, default=None, metavar="B",
+                   help="capture bits (soft: values) from one frame's start to the next (default: a frame's own)")
+    d.add_argument("--frame-offsets", default=None, metavar="FILE.npy",
+                   help=".npy of int64: where each frame begins (instead of --start and --frame-stride)")
+    d.add_argument("--start-state", type=frame_state, default=0, metavar="S|any",
+                   help="with --frame: the encoder's state before a frame, or any (default 0)")
+    d.add_argument("--end-state", type=frame_state, default=0, metavar="S|any",
+                   help="with --frame: the encoder's state after a frame, or any (default 0: m zero tail bits)")
 
     c = sub.add_parser("compare", help="P_err figures of both detectors (plots_compare.py)")
     c.add_argument("--hybrid", required=True, help="CSV of the experiment subcommand")
     c.add_argument("--baseline", required=True, help="CSV of the parity subcommand")
     c.add_argument("--outdir", default="plots")
     return ap
+
+
+def frame_state(text):
+    """--start-state / --end-state: a state number, or "any" (None)."""
+    if text == "any":
+        return None
+    try:
+        s = int(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"{text!r}: a state number, or any")
+    if s < 0:
+        raise argparse.ArgumentTypeError(f"{text!r}: a state number is not negative")
+    return s
+
+
+def parse_args(argv=None):
+    """parser().parse_args with the checks between arguments that argparse does not express."""
+    ap = parser()
+    a = ap.parse_args(argv)
+    if a.cmd == "decode":
+        if a.frame is None:
+            if (a.frame_count is not None or a.frame_stride is not None or a.frame_offsets is not None
+                    or a.start_state != 0 or a.end_state != 0):
+                ap.error("decode: --frame-count, --frame-stride, --frame-offsets, --start-state and --end-state need --frame")
+        else:
+            if a.T is not None or a.sync is not None:
+                ap.error("decode: --frame decodes frames of T steps each; it does not go with --T or --sync")
+            if a.frame_offsets is not None and a.frame_stride is not None:
+                ap.error("decode: --frame-offsets and --frame-stride exclude one another")
+            if a.format == "soft" and a.puncture is not None:
+                ap.error("decode: --frame with --format soft does not take --puncture")
+    return a
 
 
 def _init_dist():
@@ -344,6 +401,50 @@ def cmd_identify(a):
 
 
 DECODE_COLUMNS = ["T", "errors", "ber", "start_state", "end_state", "blocks", "forward_reruns", "trace_fixups"]
+FRAME_COLUMNS = ["frame", "offset", "status", "distance", "errors", "counted", "start_state", "end_state"]
+
+
+def cmd_decode_frames(a, n, m, g1):
+    """decode --frame: writes the rows of bits and a CSV row per frame."""
+    import numpy as np
+    offsets = None
+    if a.frame_offsets is not None:
+        offsets = np.load(a.frame_offsets)
+        if offsets.dtype != np.int64:
+            raise SystemExit(f"{a.frame_offsets}: frame offsets are int64, not {offsets.dtype}")
+        offsets = offsets.reshape(-1)
+    kw = dict(F=a.frame_count, start=a.start, stride=a.frame_stride, offsets=offsets, start_state=a.start_state,
+              end_state=a.end_state)
+    try:
+        if a.format == "soft":
+            res = decode_frames_soft(n, m, g1, load_soft_capture(a.input, a.nbits), a.frame, **kw)
+        else:
+            res = decode_frames(n, m, g1, load_capture(a.input), a.frame, keep=a.puncture, format=a.format,
+                                nbits=a.nbits, **kw)
+    except ValueError as e:
+        raise SystemExit(f"decode: {e}")
+    frames = res["frames"].cpu().numpy()
+    if offsets is None:
+        span = n * a.frame if a.puncture is None else punctured_bits(a.frame, puncture_pattern(a.puncture, n))
+        stride = a.frame_stride if a.frame_stride is not None else span
+        offsets = a.start + stride * np.arange(res["F"], dtype=np.int64)
+    out = a.out or os.path.join(a.save_dir, "decode_frames.csv")
+    out_bits = a.out_bits or os.path.join(a.save_dir, "decoded.npy")
+    for path in (out, out_bits):
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(out_bits, "wb") as f:             # (np.save would append .npy to another suffix)
+        np.save(f, res["bits"].cpu().numpy())
+    with open(out, "w", newline="") as f:
+        wr = csv.writer(f)
+        wr.writerow(FRAME_COLUMNS)
+        for i, r in enumerate(frames.tolist()):
+            wr.writerow([i, int(offsets[i]), r[3], r[0], r[4], r[5], r[1], r[2]])
+    print(f"Decoded {res['decoded']} frames of {res['T']} steps ({res['skipped']} skipped): distance "
+          f"{res['total_distance']}, {res['total_errors']} channel errors in {res['total_counted']} positions, "
+          f"p = {res['ber']!r}")
+    print("Saved bits to", out_bits, f"({res['F']} rows of {res['bits'].shape[1]} bytes)")
+    print("Saved results to", out)
+    return 0
 
 
 def cmd_decode(a):
@@ -356,6 +457,8 @@ def cmd_decode(a):
         raise SystemExit(f"decode: {a.code} has k = {k}; the decoder takes k = 1 codes")
     if a.sync is not None and a.puncture is None:
         raise SystemExit("decode: --sync needs --puncture")
+    if a.frame is not None:
+        return cmd_decode_frames(a, n, m, g1)
     columns = DECODE_COLUMNS
     soft = a.format == "soft"
     if soft:
@@ -420,7 +523,7 @@ def cmd_decode(a):
 
 
 def main(argv=None):
-    a = parser().parse_args(argv)
+    a = parse_args(argv)
     if a.cmd == "decode":
         return cmd_decode(a)
     if a.cmd == "scan":

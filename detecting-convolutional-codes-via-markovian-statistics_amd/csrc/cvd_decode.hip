@@ -42,7 +42,7 @@
 // normalisations (D_0 = 0 and D_T(s_T) = 0, and along the decisions D'(s') = D(ps) + d_H
 // holds exactly), integer adds in any order.  No scratch.
 // The kernel arguments, the staging helper, the pattern-independent part of a lane, the step
-// loop (acs_chunk) and the forward / join bodies are in cvd_decode_common.h: this file's Lane
+// loop (acs_chunk) and the forward / join bodies are in cvd_decode_common.h: Lane (cvd_decode_lanes.h)
 // brings the branch-metric fields, the staging and the SGPR funnel that y_t is shifted out of.
 // cvd_decode_punct.hip brings a lane, a forward and a join kernel for punctured captures and
 // runs everything else here; cvd_decode_soft.hip does the same for int8 confidence values, whose
@@ -58,72 +58,12 @@
 #include "../../include/cvd.h"
 #include "cvd_capture_bits.h"
 #include "cvd_decode_common.h"
+#include "cvd_decode_lanes.h"
 #include "cvd_internal.h"
 
 namespace {
 
-using namespace cvd::vit;   // kWave, kSeg, kStageDw, Shape, VArgs, stage_bits, LaneBase (cvd_decode_common.h)
-
-template <int m, int n>
-struct Lane : LaneBase<m> {
-  using LaneBase<m>::S;
-  using LaneBase<m>::SPL;
-  using LaneBase<m>::lane;
-  using LaneBase<m>::ps0;
-  using LaneBase<m>::ps1;
-  using LaneBase<m>::state;
-  uint32_t bm0[SPL], bm1[SPL];     // the predecessors' branch metrics: bits 2y..2y+1 = d_H(out(ps_b, u), y)
-
-  __device__ __forceinline__ void init(const VArgs& a) {
-    this->init_base();
-#pragma unroll
-    for (int i = 0; i < SPL; ++i) {
-      const int u = state(i) & 1;
-      const uint32_t o0 = this->template branch_out<n>(a, ps0[i], u), o1 = this->template branch_out<n>(a, ps1[i], u);
-      bm0[i] = bm1[i] = 0u;
-#pragma unroll
-      for (uint32_t y = 0; y < (1u << n); ++y) {
-        bm0[i] |= (uint32_t)__builtin_popcount(o0 ^ y) << (2 * y);
-        bm1[i] |= (uint32_t)__builtin_popcount(o1 ^ y) << (2 * y);
-      }
-    }
-  }
-
-  __device__ __forceinline__ int cand0(int i, uint32_t y2, int a) const { return a + (int)((bm0[i] >> y2) & 3u); }
-  __device__ __forceinline__ int cand1(int i, uint32_t y2, int a) const { return a + (int)((bm1[i] >> y2) & 3u); }
-
-  // steps [t0, t1) of Eq. 4-5 on D (not normalised); record: the decision words to
-  // dec[(t - t0) SPL + i] (acs_chunk).  Returns 0: D is the metric itself.  LDS: st kStageDw
-  // dwords, met 2 S ints (S > 64).
-  template <bool record>
-  __device__ __forceinline__ int run(const VArgs& a, int64_t t0, int64_t t1, int (&D)[SPL], uint64_t* dec,
-                                     uint32_t* st, int* met) const {
-    constexpr uint32_t ymask = (1u << n) - 1u;
-    int cur = 0;
-    for (int64_t seg = t0; seg < t1; seg += kSeg) {
-      const int cnt = (int)min((int64_t)kSeg, t1 - seg);
-      __syncthreads();                                   // the previous segment has been read
-      stage_bits(a, a.start + (int64_t)n * seg, n * cnt, st, lane);
-      __syncthreads();
-      uint32_t q = (uint32_t)((a.start + (int64_t)n * seg) & 31);
-      int dw = -1;                                       // the staged dwords dw, dw + 1 in SGPRs: y_t is scalar work
-      uint32_t wlo = 0u, whi = 0u;
-      for (int j0 = 0; j0 < cnt; j0 += kWave) {
-        acs_chunk<record>(*this, min(kWave, cnt - j0), D, cur, met, dec + ((seg - t0) + j0) * SPL, [&](int) {
-          if ((int)(q >> 5) != dw) {
-            dw = (int)(q >> 5);
-            wlo = (uint32_t)__builtin_amdgcn_readfirstlane((int)st[dw]);
-            whi = (uint32_t)__builtin_amdgcn_readfirstlane((int)st[dw + 1]);
-          }
-          const uint32_t y2 = 2u * ((uint32_t)((((uint64_t)whi << 32) | wlo) >> (q & 31u)) & ymask);
-          q += n;
-          return y2;
-        });
-      }
-    }
-    return 0;
-  }
-};
+using namespace cvd::vit;   // kWave, kSeg, kStageDw, Shape, VArgs, stage_bits, LaneBase (cvd_decode_common.h), Lane (cvd_decode_lanes.h)
 
 template <int m, int n>
 __global__ __launch_bounds__(kWave) void viterbi_forward_kernel(VArgs a) {

@@ -7,7 +7,7 @@
 // The step loop and the two kernels' bodies are cvd_decode_common.h's (acs_chunk, forward_body,
 // join_body), the pattern's checks and packing cvd_decode.hip's (cvd::viterbi_pack_pattern).
 //
-// What PLane brings where cvd_decode.hip's Lane has its funnel and 2-bit metric fields:
+// What PLane (cvd_decode_lanes.h) brings where Lane has its funnel and 2-bit metric fields:
 //   staging   a segment of kSeg steps covers the bits [pos(seg), pos(seg + cnt)), never more
 //             than n cnt; once its dwords are in LDS the lanes resolve the pattern, 16 steps
 //             each: the step's column (a segment, a warm-up, a block or a rerun may begin in
@@ -27,6 +27,7 @@
 #include "../../include/cvd.h"
 #include "cvd_capture_bits.h"
 #include "cvd_decode_common.h"
+#include "cvd_decode_lanes.h"
 #include "cvd_internal.h"
 
 namespace {
@@ -34,107 +35,6 @@ namespace {
 using namespace cvd::vit;
 
 constexpr const char* kWho = "viterbi_decode_punctured";
-
-// pos(t) of include/cvd.h, t in 0..2^31 - 1
-__device__ __forceinline__ int64_t pos_of(const VArgs& a, int64_t t, uint32_t* col) {
-  const uint32_t tt = (uint32_t)t, per = (uint32_t)a.period;
-  const uint32_t r = tt / per, c = tt - r * per;
-  *col = c;
-  const uint32_t pre = (uint32_t)(a.ppre[c >> 3] >> (8u * (c & 7u))) & 255u;
-  return a.start + (int64_t)r * a.K + pre;
-}
-
-template <int m, int n>
-struct PLane : LaneBase<m> {
-  using LaneBase<m>::S;
-  using LaneBase<m>::SPL;
-  using LaneBase<m>::lane;
-  using LaneBase<m>::ps0;
-  using LaneBase<m>::ps1;
-  using LaneBase<m>::state;
-  uint32_t o0[SPL], o1[SPL];       // the outputs of the lane's two branches
-
-  __device__ __forceinline__ void init(const VArgs& a) {
-    this->init_base();
-#pragma unroll
-    for (int i = 0; i < SPL; ++i) {
-      const int u = state(i) & 1;
-      o0[i] = this->template branch_out<n>(a, ps0[i], u);
-      o1[i] = this->template branch_out<n>(a, ps1[i], u);
-    }
-  }
-
-  // y: a step's byte, y_t | keep << 4
-  __device__ __forceinline__ int cand0(int i, uint32_t y, int a) const {
-    return __builtin_popcount((o0[i] ^ y) & (y >> 4) & 7u) + a;
-  }
-  __device__ __forceinline__ int cand1(int i, uint32_t y, int a) const {
-    return __builtin_popcount((o1[i] ^ y) & (y >> 4) & 7u) + a;
-  }
-
-  // steps [t0, t1) of Eq. 4-5 with the pattern's metric on D (not normalised); record, met and
-  // the result as in cvd_decode.hip's Lane::run.  LDS: st kPunctStageDw dwords: the segment's
-  // capture dwords, then a byte per step, y_t | keep << 4.
-  template <bool record>
-  __device__ __forceinline__ int run(const VArgs& a, int64_t t0, int64_t t1, int (&D)[SPL], uint64_t* dec,
-                                     uint32_t* st, int* met) const {
-    int cur = 0;
-    uint32_t* sy = st + kStageDw;
-    const uint32_t per = (uint32_t)a.period, q64 = (uint32_t)kWave / per, r64 = (uint32_t)kWave - q64 * per;
-    for (int64_t seg = t0; seg < t1; seg += kSeg) {
-      const int cnt = (int)min((int64_t)kSeg, t1 - seg);
-      uint32_t c0, c1;
-      const int64_t p0 = pos_of(a, seg, &c0), p1 = pos_of(a, seg + cnt, &c1);
-      __syncthreads();                                   // the previous segment has been read
-      stage_bits(a, p0, (int)(p1 - p0), st, lane);
-      __syncthreads();
-      // lane l: steps seg + l, seg + l + 64, ...: the step's period and column (one division,
-      // then 64 steps further each time), its bits out of the staged dwords, spread
-      {
-        const uint32_t tt = (uint32_t)seg + (uint32_t)lane;
-        uint32_t rr = tt / per, c = tt - rr * per;
-        const int64_t base = a.start - ((p0 >> 5) << 5);     // pos(t) - base: the bit's place in st
-        for (int i = lane; i < cnt; i += kWave) {
-          const uint32_t pre = (uint32_t)(a.ppre[c >> 3] >> (8u * (c & 7u))) & 255u;
-          const uint32_t off = (uint32_t)(base + (int64_t)rr * a.K) + pre;   // < 32 + 3 kSeg
-          const uint32_t keep = (uint32_t)(a.pmask >> (4u * c)) & 7u;
-          uint32_t r = (uint32_t)((((uint64_t)st[(off >> 5) + 1] << 32) | st[off >> 5]) >> (off & 31u));
-          uint32_t y = 0u;                               // the kept bits, j ascending, into their positions j
-#pragma unroll
-          for (int j = 0; j < n; ++j) {
-            const uint32_t k = (keep >> j) & 1u;
-            y |= (r & k) << j;
-            r >>= k;
-          }
-          reinterpret_cast<uint8_t*>(sy)[i] = (uint8_t)(y | (keep << 4));
-          rr += q64;
-          c += r64;
-          if (c >= per) {
-            c -= per;
-            ++rr;
-          }
-        }
-      }
-      __syncthreads();
-      int dw = -1;                                       // eight steps' bytes in an SGPR pair: y_t, keep are scalar work
-      uint32_t wlo = 0u, whi = 0u;
-      for (int j0 = 0; j0 < cnt; j0 += kWave) {
-        acs_chunk<record>(*this, min(kWave, cnt - j0), D, cur, met, dec + ((seg - t0) + j0) * SPL, [&](int jj) {
-          const int j = j0 + jj;
-          if ((j >> 3) != dw) {
-            dw = j >> 3;
-            wlo = (uint32_t)__builtin_amdgcn_readfirstlane((int)sy[2 * dw]);
-            whi = (uint32_t)__builtin_amdgcn_readfirstlane((int)sy[2 * dw + 1]);
-          }
-          return (uint32_t)((((uint64_t)whi << 32) | wlo) >> (8u * ((uint32_t)j & 7u)));
-        });
-      }
-    }
-    return 0;
-  }
-};
-
-constexpr int kPunctStageDw = kStageDw + kSeg / 4;
 
 template <int m, int n>
 __global__ __launch_bounds__(kWave) void viterbi_punct_forward_kernel(VArgs a) {

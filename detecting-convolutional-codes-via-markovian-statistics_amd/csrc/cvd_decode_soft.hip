@@ -7,7 +7,7 @@
 // two kernels' bodies are cvd_decode_common.h's (acs_chunk, forward_body, join_body): SLane
 // overrides the four vector members and norm_of, and its run returns sum_t A_t.
 //
-// What SLane brings where cvd_decode.hip's Lane has its funnel and 2-bit metric fields:
+// What SLane (cvd_decode_lanes.h) brings where Lane has its funnel and 2-bit metric fields:
 //   metric    cost(out, t) = sum_j a(v_j) [v_j != 0 and (v_j > 0) != bit j of out], a(v) =
 //             min(|v|, 127).  With corr = sum_j (+-1 by bit j of out) v_j and A_t = sum_j a(v_j),
 //             2 cost = A_t - corr, and A_t is the same for every state: the loop carries
@@ -31,6 +31,7 @@
 
 #include "../../include/cvd.h"
 #include "cvd_decode_common.h"
+#include "cvd_decode_lanes.h"
 #include "cvd_internal.h"
 
 namespace {
@@ -39,112 +40,7 @@ using namespace cvd::vit;
 
 constexpr const char* kWho = "viterbi_decode_soft";
 constexpr const char* kWhoDep = "soft_depuncture";
-constexpr int kSoftStageU4 = 3 * kSeg / 16 + 2;   // n <= 3: the segment's 16-byte pieces and alignment slack
 constexpr int64_t kMaxSpan = 1 << 20;             // block + warm: 2 * 127 * 3 * 2^20 < 2^30
-
-template <int m, int n>
-struct SLane : LaneBase<m> {
-  using LaneBase<m>::S;
-  using LaneBase<m>::SPL;
-  using LaneBase<m>::lane;
-  using LaneBase<m>::ps0;
-  using LaneBase<m>::ps1;
-  using LaneBase<m>::state;
-  int pat0[SPL], pat1[SPL];        // byte j < n: -1 if bit j of the branch's output is 1, else +1; 0 above
-
-  __device__ __forceinline__ static int pattern(uint32_t out) {
-    uint32_t p = 0u;
-#pragma unroll
-    for (int j = 0; j < n; ++j) p |= (((out >> j) & 1u) ? 0xffu : 0x01u) << (8 * j);
-    return (int)p;
-  }
-
-  __device__ __forceinline__ void init(const VArgs& a) {
-    this->init_base();
-#pragma unroll
-    for (int i = 0; i < SPL; ++i) {
-      const int u = state(i) & 1;
-      pat0[i] = pattern(this->template branch_out<n>(a, ps0[i], u));
-      pat1[i] = pattern(this->template branch_out<n>(a, ps1[i], u));
-    }
-  }
-
-  // The loop's x = 2 D - sum A_t; the vectors in memory are D, 16-bit, and the end vector also
-  // the byte min(D, 255) that look and fix test for zero.
-  __device__ __forceinline__ void store16(uint16_t* vec, uint8_t* bytes, const int (&X)[SPL]) const {
-    if (lane < S) {
-#pragma unroll
-      for (int i = 0; i < SPL; ++i) {
-        const int d = X[i] >> 1;
-        vec[state(i)] = (uint16_t)d;
-        if (bytes) bytes[state(i)] = (uint8_t)min(d, 255);
-      }
-    }
-  }
-  __device__ __forceinline__ void store_warm(const VArgs& a, int64_t b, const int (&X)[SPL]) const {
-    store16(a.warm16 + b * S, nullptr, X);
-  }
-  __device__ __forceinline__ void store_end(const VArgs& a, int64_t b, const int (&X)[SPL]) const {
-    store16(a.end16 + b * S, a.endv + b * S, X);
-  }
-  __device__ __forceinline__ void load_end(const VArgs& a, int64_t b, int (&X)[SPL]) const {
-#pragma unroll
-    for (int i = 0; i < SPL; ++i) X[i] = 2 * (int)a.end16[b * S + state(i)];
-  }
-  __device__ __forceinline__ bool differs_from_warm(const VArgs& a, int64_t b, const int (&X)[SPL]) const {
-    bool diff = false;
-#pragma unroll
-    for (int i = 0; i < SPL; ++i) diff |= X[i] != 2 * (int)a.warm16[b * S + state(i)];
-    return diff;
-  }
-  __device__ __forceinline__ static int norm_of(int mn, int asum) { return (mn + asum) >> 1; }
-
-  // vs: a step's n values, packed
-  __device__ __forceinline__ int cand0(int i, int vs, int x) const { return __builtin_amdgcn_sdot4(pat0[i], vs, x, false); }
-  __device__ __forceinline__ int cand1(int i, int vs, int x) const { return __builtin_amdgcn_sdot4(pat1[i], vs, x, false); }
-
-  // steps [t0, t1) on x (not normalised); record as in cvd_decode.hip's Lane::run.  Returns the
-  // sum of A_t over the steps.  LDS: st kSoftStageU4 pieces, met 2 S ints (S > 64).
-  template <bool record>
-  __device__ __forceinline__ int run(const VArgs& a, int64_t t0, int64_t t1, int (&X)[SPL], uint64_t* dec, uint4* st,
-                                     int* met) const {
-    int cur = 0;
-    int asum = 0;                                        // this lane's share of sum A_t
-    const int8_t* sb = reinterpret_cast<const int8_t*>(st);
-    for (int64_t seg = t0; seg < t1; seg += kSeg) {
-      const int cnt = (int)min((int64_t)kSeg, t1 - seg);
-      const int64_t p0 = a.start + (int64_t)n * seg;     // the segment's first value
-      const int64_t g0 = p0 >> 4;
-      const int off = (int)(p0 & 15);
-      const int npc = (off + n * cnt + 15) >> 4;         // <= kSoftStageU4 - 1
-      __syncthreads();                                   // the previous segment has been read
-      for (int i = lane; i < npc; i += kWave) {
-        uint4 v = make_uint4(0u, 0u, 0u, 0u);
-        if (g0 + i < a.nu4) v = a.cap[g0 + i];
-        st[i] = v;
-      }
-      __syncthreads();
-      for (int j0 = 0; j0 < cnt; j0 += kWave) {
-        const int c64 = min(kWave, cnt - j0);
-        int vp = 0;                                      // lane j: the n values of the chunk's step j, packed
-        if (lane < c64) {
-          const int8_t* p = sb + off + n * (j0 + lane);
-#pragma unroll
-          for (int j = 0; j < n; ++j) {
-            const int v = max((int)p[j], -127);
-            asum += abs(v);
-            vp |= (v & 255) << (8 * j);
-          }
-        }
-        acs_chunk<record>(*this, c64, X, cur, met, dec + ((seg - t0) + j0) * SPL,
-                          [&](int jj) { return __builtin_amdgcn_readlane(vp, jj); });
-      }
-    }
-#pragma unroll
-    for (int k = 1; k < kWave; k <<= 1) asum += __shfl_xor(asum, k);
-    return asum;
-  }
-};
 
 template <int m, int n>
 __global__ __launch_bounds__(kWave) void viterbi_soft_forward_kernel(VArgs a) {

@@ -20,6 +20,12 @@ Soft captures (one int8 confidence value per channel bit, 0 = erased) go through
 cvd_viterbi_decode_soft (csrc/cvd_decode_soft.hip): decode_capture_soft decodes, with keep=...
 after depuncturing on the device (depuncture_soft); soft_from_bits turns hard bits into such a
 capture and sync_punctured_soft is sync_punctured's loop.
+
+Framed captures (802.11a/g PPDUs, GSM bursts, packets: each frame starts in a known state and
+is driven back to one by m tail bits) go through cvd_viterbi_decode_frames and its punctured
+and soft siblings (csrc/cvd_decode_frames.hip): decode_frames and decode_frames_soft decode a
+batch of F frames of T steps, at a stride or at given offsets, in one call, with the start and
+end states told to the decoder.
 """
 import ctypes
 
@@ -354,3 +360,125 @@ def sync_punctured_soft(n, m, gen, keep, soft, start=0, T=1000, block=None, warm
         r["offset"] = o
         res.append(r)
     return sorted(res, key=lambda r: (r["metric"], r["offset"]))
+
+
+# ───────────────────────────── framed captures ──────────────────────────────
+
+FRAME_MAX_T = 65536      # include/cvd.h CVD_VITERBI_FRAME_MAX_T
+FRAME_ANY = -1           # include/cvd.h CVD_FRAME_ANY
+
+
+def _frame_state(name, s, m):
+    """A boundary state as the library takes it: None is CVD_FRAME_ANY."""
+    if s is None:
+        return FRAME_ANY
+    s = int(s)
+    if not 0 <= s < (1 << m):
+        raise ValueError(f"{name} = {s}: a state in [0, {1 << m}), or None for any")
+    return s
+
+
+def _frames(who, entry, lead, fmt, cap, nbits, n, m, T, span, F, start, stride, offsets, start_state, end_state, soft,
+            dev):
+    """One call of the library's frame decoder `entry`(*lead, capture, nbits, *fmt, start, stride,
+    offsets, F, T, start_state, end_state, bits, frames, stats, work, stream): decode_frames' dict.
+    span: the capture bits (values) of a frame."""
+    T = int(T)
+    if not 1 <= T <= FRAME_MAX_T:
+        raise ValueError(f"T = {T}: a frame has 1..{FRAME_MAX_T} steps")
+    ss, es = _frame_state("start_state", start_state, m), _frame_state("end_state", end_state, m)
+    if ss >= 0 and es >= 0 and T < m:
+        raise ValueError(f"T = {T} < m = {m}: with both states fixed the end state is not reachable")
+    w = (T + 31) // 32
+    off = None
+    if offsets is not None:
+        off = torch.from_numpy(np.ascontiguousarray(offsets)) if isinstance(offsets, np.ndarray) else offsets
+        if not isinstance(off, torch.Tensor) or off.dtype != torch.int64:
+            raise TypeError("offsets is a numpy array or torch tensor of int64")
+        off = off.reshape(-1).to(dev).contiguous()
+        if F is not None and int(F) != off.numel():
+            raise ValueError(f"F = {F} but {off.numel()} offsets")
+        F, start, stride = off.numel(), 0, 1
+    else:
+        start = int(start)
+        stride = span if stride is None else int(stride)
+        if start < 0 or stride < 1:
+            raise ValueError("needs start >= 0 and stride >= 1")
+        fit = (nbits - start - span) // stride + 1 if nbits - start >= span else 0
+        F = fit if F is None else int(F)
+        if not 0 <= F <= fit:
+            raise ValueError(f"F = {F}: {fit} frames of {span} capture positions fit from {start} at stride {stride}")
+    if F * w >= 1 << 31:
+        raise ValueError(f"F = {F} frames of {w} words: the decoded bits must stay below 2^31 words")
+    L = _lib.lib()
+    call = getattr(L, entry)
+    wbytes = int(L.cvd_viterbi_frames_workspace_bytes(n, m, T, F, int(soft)))
+    if wbytes < 0:
+        # the decoder itself names an unsupported code shape
+        _lib.check(call(*lead, None, 0, *fmt, 0, 1, None, 0, T, ss, es, None, None, None, None, None))
+        _lib.check(wbytes)
+    with torch.cuda.device(dev):
+        bits = torch.empty((F, 4 * w), dtype=torch.uint8, device=dev)
+        frames = torch.empty((F, 6), dtype=torch.int32, device=dev)
+        s = [0, 0, 0, 0, 0, w]
+        if F:
+            free = torch.cuda.mem_get_info(dev)[0]
+            if wbytes > free:
+                raise MemoryError(f"{who}: the workspace of {F} frames of T = {T} steps (m = {m}) is {wbytes} bytes, "
+                                  f"{free} bytes of device memory are free: decode the frames in pieces")
+            stats = torch.zeros(6, dtype=torch.int64, device=dev)
+            work = torch.empty(max(wbytes, 16), dtype=torch.uint8, device=dev)
+            _lib.check(call(*lead, ctypes.c_void_p(cap.data_ptr()), nbits, *fmt, start, stride,
+                            ctypes.c_void_p(off.data_ptr()) if off is not None else None, F, T, ss, es,
+                            ctypes.c_void_p(bits.data_ptr()), ctypes.c_void_p(frames.data_ptr()),
+                            ctypes.c_void_p(stats.data_ptr()), ctypes.c_void_p(work.data_ptr()), _stream_ptr()))
+            s = stats.cpu().tolist()     # synchronises: cap, off and work may be freed on return
+    return {"bits": bits, "frames": frames, "distance": frames[:, 0], "start_states": frames[:, 1],
+            "end_states": frames[:, 2], "status": frames[:, 3], "errors": frames[:, 4], "counted": frames[:, 5],
+            "T": T, "F": F, "decoded": int(s[1]), "skipped": int(s[2]), "total_distance": int(s[0]),
+            "total_errors": int(s[3]), "total_counted": int(s[4]), "words": int(s[5]), "ber": s[3] / s[4] if s[4] else 0.0}
+
+
+def decode_frames(n, m, gen, capture, T, F=None, start=0, stride=None, offsets=None, start_state=0, end_state=0,
+                  keep=None, format="bytes", nbits=None, device=None):
+    """cvd_viterbi_decode_frames: F frames of T steps each of the k = 1 code gen[j][i][d], decoded
+    in one call.  Frame f begins at capture bit start + f*stride (stride=None: the frames follow
+    one another, stride = the capture bits of a frame; F=None: as many frames as fit), or at
+    offsets[f] (a numpy array or torch tensor of int64; a frame that does not lie inside the
+    capture is skipped).  start_state / end_state: the state the encoder was in before / after
+    the frame, None for unknown; the defaults are terminated frames (m zero tail bits).
+    keep (anything puncture_pattern takes): the frames are punctured
+    (cvd_viterbi_decode_frames_punctured), the pattern restarting at column 0 in every frame.
+    Returns a dict: bits (device uint8 [F, 4w], w = ceil(T/32): row f LSB-packed), frames (device
+    int32 [F, 6]) and the views of its columns distance, start_states, end_states, status (0
+    decoded, 1 skipped), errors, counted; T, F, words (w), decoded, skipped, total_distance,
+    total_errors, total_counted and ber = total_errors / total_counted."""
+    dev = device if isinstance(device, torch.device) else _require_gpu(device)
+    n, m, T = int(n), int(m), int(T)
+    code = as_code(gen, m, 1, n)
+    cap, fmt, nbits = capture_buffer(capture, format, nbits, dev)
+    if keep is None:
+        return _frames("decode_frames", "cvd_viterbi_decode_frames", (code.c,), (fmt,), cap, nbits, n, m, T, n * T, F,
+                       start, stride, offsets, start_state, end_state, False, dev)
+    keep = puncture_pattern(keep, n)
+    return _frames("decode_frames", "cvd_viterbi_decode_frames_punctured", (code.c, bytes(keep), len(keep)), (fmt,), cap,
+                   nbits, n, m, T, punctured_bits(max(T, 0), keep), F, start, stride, offsets, start_state, end_state,
+                   False, dev)
+
+
+def decode_frames_soft(n, m, gen, soft, T, F=None, start=0, stride=None, offsets=None, start_state=0, end_state=0,
+                       keep=None, device=None):
+    """cvd_viterbi_decode_frames_soft: decode_frames over a soft capture (int8, as
+    decode_capture_soft takes it); start, stride and offsets count values.  distance is the soft
+    distance of a frame's path, errors its sign disagreements, counted its non-erased values.
+    Punctured soft frames are not depunctured frame by frame: keep raises NotImplementedError
+    (slice the values to bits and use decode_frames(keep=...))."""
+    if keep is not None:
+        raise NotImplementedError("decode_frames_soft does not depuncture frame by frame: slice the values to hard "
+                                  "bits and use decode_frames(keep=...)")
+    dev = device if isinstance(device, torch.device) else _require_gpu(device)
+    n, m, T = int(n), int(m), int(T)
+    code = as_code(gen, m, 1, n)
+    cap, nvals = _soft_buffer(soft, dev)
+    return _frames("decode_frames_soft", "cvd_viterbi_decode_frames_soft", (code.c,), (), cap, nvals, n, m, T, n * T, F,
+                   start, stride, offsets, start_state, end_state, True, dev)

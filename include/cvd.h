@@ -588,6 +588,82 @@ int cvd_soft_depuncture(const int8_t* d_in, int64_t nvals, int64_t start,
                         const uint8_t* keep, int32_t period, int32_t n, int64_t T,
                         int8_t* d_out, void* stream);
 
+/* ---- framed captures: a batch of terminated frames in one call (nothing in the reference) ----
+ * 802.11a/g PPDUs, GSM bursts, CCSDS / AX.25-style packets and LTE control blocks are frames: a
+ * frame starts in a known state (0) and is driven back to a known state by m tail bits, and a
+ * capture holds thousands to millions of them, at a regular stride or at offsets that a
+ * sync-word search found.  These calls decode F frames of T steps each in one launch, with the
+ * boundary states told to the decoder.
+ * Inherited: the code shapes (k = 1, n in {2, 3}, 1 <= m <= 8, else CVD_E_UNSUPPORTED), the
+ * capture formats with their 16-byte alignment and readability rule, states and branches, the
+ * tie rule (`val < best`, ties keep b = 0) and the metric of each flavour are
+ * cvd_viterbi_decode's, cvd_viterbi_decode_punctured's (keep, period, pos) and
+ * cvd_viterbi_decode_soft's (-128 is read as -127, 0 is an erasure).  Nothing in those three
+ * calls changes.
+ * Frames: frame f, 0 <= f < F, begins at capture bit (soft: value) o_f = start + f*stride when
+ * d_offsets is null, else at o_f = d_offsets[f] (a device array of F int64, 8-byte aligned;
+ * start and stride are then ignored).  Every frame has T steps, 1 <= T <= 65536.  Step t of
+ * frame f reads capture bits o_f + n*t + j; in the punctured call it reads at pos(t) of that
+ * contract with o_f in the place of start, so the pattern restarts at column 0 in every frame.
+ * span = n*T, in the punctured call pos(T) - start.  Frames may overlap or repeat; the capture
+ * is only read. */
+#define CVD_VITERBI_FRAME_MAX_T 65536
+#define CVD_FRAME_ANY (-1)
+/* Boundary conditions (metrics unnormalised, over the integers extended by +inf):
+ *   start_state = CVD_FRAME_ANY: D_0(s) = 0 for every s;
+ *   start_state = s0 in [0, 2^m): D_0(s0) = 0 and D_0(s) = +inf elsewhere;
+ *   end_state = CVD_FRAME_ANY: s_T is the lowest-index state with minimal D_T;
+ *   end_state = e in [0, 2^m): s_T = e.
+ * The recursion (without the normalisation), the traceback and u_t are cvd_viterbi_decode's.
+ * Any implementation constant larger than every finite path metric gives the same result as
+ * +inf: a state of finite metric has a predecessor of finite metric, which wins its comparison,
+ * so the traced path never passes through a state of infinite metric and the decisions at such
+ * states are never read.  With both states fixed T >= m is required, so that e is reachable.
+ * d_bits: F rows of w = ceil(T/32) words, bit t of row f = u_t LSB first, padding bits zero.
+ * d_frames: int32[F][6], 4-byte aligned:
+ *   [0] the distance D_T(s_T): the Hamming distance, the Hamming distance over the kept bits,
+ *       or the soft distance    [1] s_0 as traced    [2] s_T    [3] status: 0 decoded, 1 skipped
+ *   [4] hard errors: equal to [0] for hard and punctured frames; soft: the sign disagreements
+ *       of the traced path    [5] counted positions: n*T, the kept bits, or the non-erased values
+ * d_stats: int64[6], written (not accumulated), 8-byte aligned:
+ *   [0] sum of distances  [1] frames decoded  [2] frames skipped  [3] sum of hard errors
+ *   [4] sum of counted  [5] w
+ * stats[3] / stats[4] estimates the channel's crossover probability.  All sums are integer, so
+ * the result does not depend on the launch shape.
+ * Skipped frames (offset mode only): a frame with o_f < 0 or o_f + span > nbits is not decoded;
+ * its row of bits is zero, its record {0, -1, -1, 1, 0, 0}, and nothing is read for it.
+ * CVD_E_INVALID, before the device is touched, cvd_last_error() naming viterbi_decode_frames
+ * (_punctured, _soft), for: an unknown format; nbits < 0; F < 0; start_state or end_state
+ * outside {-1} u [0, 2^m); in stride mode start < 0 or stride < 1; and when F > 0: T outside
+ * 1..65536; both states fixed and T < m; F*w >= 2^31 words; in stride mode
+ * start + (F-1)*stride + span > nbits or an int64 overflow on the way; null or misaligned
+ * pointers (d_capture, d_work 16-byte, d_stats, d_offsets 8-byte, d_bits, d_frames 4-byte
+ * aligned).  The punctured call reports a bad pattern as cvd_viterbi_decode_punctured does.
+ * F == 0: CVD_OK without a launch (nothing is written).
+ * d_work: cvd_viterbi_frames_workspace_bytes(n, m, T, F, soft) bytes, 16-byte aligned: the
+ * decision words of the frames (T rounded up to 64 steps of max(8, 2^m / 8) bytes), of at most
+ * a batch of about 1 GiB (the environment variable CVD_FRAMES_BATCH_BYTES, read at both calls,
+ * sets another size; never less than 64 frames), which the call goes through batch after batch
+ * on `stream`; the result does not depend on the batch.  0 at
+ * F == 0; < 0 with the error set for n, m outside the shapes, T outside 1..65536, F < 0 or
+ * soft outside {0, 1}.  A size of 0 allows a null d_work.  Asynchronous on `stream`.
+ * Kernels: csrc/cvd_decode_frames.hip. */
+int64_t cvd_viterbi_frames_workspace_bytes(int32_t n, int32_t m, int32_t T, int64_t F, int32_t soft);
+int cvd_viterbi_decode_frames(const cvd_code* code, const void* d_capture, int64_t nbits, int32_t format,
+                              int64_t start, int64_t stride, const int64_t* d_offsets, int64_t F, int32_t T,
+                              int32_t start_state, int32_t end_state,
+                              uint32_t* d_bits, int32_t* d_frames, int64_t* d_stats, void* d_work, void* stream);
+int cvd_viterbi_decode_frames_punctured(const cvd_code* code, const uint8_t* keep, int32_t period,
+                                        const void* d_capture, int64_t nbits, int32_t format,
+                                        int64_t start, int64_t stride, const int64_t* d_offsets, int64_t F, int32_t T,
+                                        int32_t start_state, int32_t end_state,
+                                        uint32_t* d_bits, int32_t* d_frames, int64_t* d_stats, void* d_work,
+                                        void* stream);
+int cvd_viterbi_decode_frames_soft(const cvd_code* code, const int8_t* d_soft, int64_t nvals,
+                                   int64_t start, int64_t stride, const int64_t* d_offsets, int64_t F, int32_t T,
+                                   int32_t start_state, int32_t end_state,
+                                   uint32_t* d_bits, int32_t* d_frames, int64_t* d_stats, void* d_work, void* stream);
+
 /* ---- error-exponent engine (alpha_exponent.py, Eq. 7) ---------------------
  * Joint counts of (metric state i, received word r) along received streams
  * (pitch = nseq) for steps t >= burn_in, on a dense (enumerated) model with
