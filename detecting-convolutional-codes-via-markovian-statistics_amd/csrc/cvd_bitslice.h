@@ -98,6 +98,7 @@ constexpr unsigned kTtOr3 = 0xFE;      // a | b | c
 constexpr unsigned kTtAndXor = 0x28;   // (a ^ b) & c   (not used by the kernel; tests)
 constexpr unsigned kTtSel = 0xCA;      // a ? b : c, bitwise (v_bfi_b32)
 constexpr unsigned kTtAndNotOr = 0xBA; // (a & ~b) | c
+constexpr unsigned kTtXorAndN = 0x14;  // (a ^ b) & ~c
 
 // v_perm_b32(hi, lo, sel): byte i of the result = byte sel_i of the 8-byte hi:lo (sel 12 = 0)
 CVD_HD bs_u32 bs_perm(bs_u32 hi, bs_u32 lo, bs_u32 sel) {
@@ -349,6 +350,84 @@ CVD_HD void bs_partner(const bs_u32 (&R)[2][4], bs_u32 (&P)[2][4]) {
   }
 }
 
+// ───────────────────── the T_ref count of a step ─────────────────────
+// c = 1 + [sym == 0] + 2 [uni and halves equal] (bs_step_core), sym = the halves differences dh
+// of D_{t-1} (all four planes of R ^ P) on the butterflies whose e is even.
+//
+// CVD_BS_TREF_FAST (default 1): the exact count only in the wave-steps where some lane passes a
+// one-plane necessary test; every other wave-step has c = 1 in all of its lanes, and the callers
+// add the constant s_lt[1].  0: the exact count in every lane at every step (the code before,
+// for A/Bs and tests).
+//   The test: x = ((R[0][i] ^ P[0][i]) & ~e0[0]) | ((R[1][i] ^ P[1][i]) & ~e0[1]) for the ONE
+//   plane i = kBsTrefPlane; a lane is a suspect iff x == 0.
+//   Why it never misses: c > 1 needs sym == 0 -- directly for the [sym == 0] term, and for the
+//   uni term because dh[0] | dh[1] == 0 makes sym (= dh masked by ~e0) zero too.  sym is the OR
+//   over the four planes of that plane's masked difference, so sym == 0 makes every plane's
+//   masked difference, x among them, zero: a lane with c > 1 is always a suspect.
+//   Which plane (profiles/tref_suspects.py, the host step over the C oracle's streams, six p,
+//   H1 and H2, 256 sequences x 4,096 steps, steps >= 64): plane 1 puts a suspect into <= 0.34% of
+//   the 64-lane wave-steps at every point; planes 0 and 3 pass in every wave-step (plane 0's
+//   partner parity is all but fixed once the survivors have merged, plane 3 is almost always
+//   clear) and plane 2 in 0.06% (p = 0.01, H1) to 100% (H2, p >= 0.15).
+#ifndef CVD_BS_TREF_FAST
+#define CVD_BS_TREF_FAST 1
+#endif
+constexpr int kBsTrefPlane = 1;
+// halves difference of word r: the states of D_{t-1} that differ from their partner
+CVD_HD bs_u32 bs_halves_diff(const bs_u32 (&R)[4], const bs_u32 (&P)[4]) {
+  bs_u32 x = R[3] ^ P[3];
+  x = bs_bop3<kTtXorOr>(R[2], P[2], x);
+  x = bs_bop3<kTtXorOr>(R[1], P[1], x);
+  return bs_bop3<kTtXorOr>(R[0], P[0], x);
+}
+CVD_HD bs_u32 bs_tref_of(const bs_u32 (&dh)[2], const bs_u32 (&e0)[2], bool uni) {
+  const bs_u32 sym = bs_bop3<kTtAndNotOr>(dh[0], e0[0], dh[1] & ~e0[1]);
+  return 1u + (sym == 0u ? 1u : 0u) + ((uni && (dh[0] | dh[1]) == 0u) ? 2u : 0u);
+}
+// does any lane of the wave hold v (host: the one lane)
+CVD_HD bool bs_wave_any(bool v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __builtin_amdgcn_ballot_w64(v) != 0ull;
+#else
+  return v;
+#endif
+}
+// the one-plane test word x of a lane (zero: a suspect)
+template <int PH>
+CVD_HD bs_u32 bs_tref_test(const bs_u32 (&R)[2][4], const bs_u32 (&P)[2][4], const bs_u32 (&e0)[2]) {
+  constexpr int i = kBsTrefPlane;
+  if constexpr (bs_sigma(PH, 5) == 5) {   // the partner is the other word
+    return bs_bop3<kTtAndX>(~(e0[0] & e0[1]), R[0][i], R[1][i]);
+  } else {
+    const bs_u32 t = bs_bop3<kTtXorAndN>(R[1][i], P[1][i], e0[1]);
+    return bs_bop3<kTtAndNotOr>(R[0][i] ^ P[0][i], e0[0], t);
+  }
+}
+// the count behind the test; all1 (wave-uniform): no lane was a suspect, so c = 1 in every lane.
+// (On all1 the kernel's c is NOT 1 but the test word x, a value already in a register: its callers
+// add the constant for c = 1 on all1 and read c only otherwise, and c = 1 here was a v_mov per
+// step for a value nobody reads.  The host sets c = 1.)
+template <int PH, bool kUni>
+CVD_HD void bs_tref_count(const bs_u32 (&R)[2][4], const bs_u32 (&P)[2][4], const bs_u32 (&e0)[2], bs_u32& c,
+                          bool& all1) {
+  const bs_u32 x = bs_tref_test<PH>(R, P, e0);
+  all1 = !bs_wave_any(x == 0u);
+  if (__builtin_expect(!all1, 0)) {
+    bs_u32 dh[2];
+    dh[0] = bs_halves_diff(R[0], P[0]);
+    dh[1] = bs_sigma(PH, 5) == 5 ? dh[0] : bs_halves_diff(R[1], P[1]);
+    c = bs_tref_of(dh, e0, kUni);
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("" : "+v"(c));   // (c as one value of this branch: no part of it is set on the other path)
+#endif
+  }
+#if !defined(__HIP_DEVICE_COMPILE__)
+  else c = 1u;
+#else
+  else c = x;
+#endif
+}
+
 // Result of one step beyond the new planes: mu (0 / 1), the T_ref count c of D_t(y)
 // among the 2^n words, and the new vector's canonical digest hash (ph, pl).
 struct BsStepOut {
@@ -363,12 +442,15 @@ struct BsStepOut {
 //   equal and the code is uni: c = 1 + [sym == 0] + 2 [uni and halves equal].
 // mid(x): called between the two words' ACS with a value that depends on the first word's
 // result (the kernel issues its filter-positive loads there)
+// all1 (optional, CVD_BS_TREF_FAST): set where no lane of the wave was a suspect of the T_ref
+// test -- every lane's count is 1 and the kernel's c is then not to be read (bs_tref_count)
 struct BsNoMid {
   CVD_HD void operator()(bs_u32) const {}
 };
 template <int PH, bool kUni, class Mid = BsNoMid>
 CVD_HD void bs_step_core(const bs_u32 (&R)[2][4], const bs_u32 (&e0)[2], const bs_u32 (&e1)[2],
-                         const bs_u32 (&ez)[2], bs_u32 (&N)[2][4], bs_u32& mu, bs_u32& c, Mid mid = Mid()) {
+                         const bs_u32 (&ez)[2], bs_u32 (&N)[2][4], bs_u32& mu, bs_u32& c, Mid mid = Mid(),
+                         bool* all1 = nullptr) {
   constexpr int L5 = bs_sigma(PH, 5);
   // mu first: a zero state with e even
   bs_u32 z[2];
@@ -382,6 +464,9 @@ CVD_HD void bs_step_core(const bs_u32 (&R)[2][4], const bs_u32 (&e0)[2], const b
   bs_u32 P[2][4];
   bs_partner<PH>(R, P);
   bs_u32 dh[2] = {0u, 0u};
+  bool one = false;
+  (void)dh; (void)L5;
+  if constexpr (CVD_BS_TREF_FAST != 0) bs_tref_count<PH, kUni>(R, P, e0, c, one);
   for (int r = 0; r < 2; ++r) {
     // own branch e - mu, partner branch 2 - e - mu (4-bit two's complement):
     //   mu = 0: own (e0, e1, 0, 0), partner (e0, ez, 0, 0)
@@ -394,18 +479,11 @@ CVD_HD void bs_step_core(const bs_u32 (&R)[2][4], const bs_u32 (&e0)[2], const b
     bs_add(P[r], e0[r], M, p1, p23, b);
     bs_min(a, b, N[r]);
     // halves differences of D_{t-1} (a state and its partner differ)
-    if (L5 != 5 || r == 0) {
-      bs_u32 x = R[r][3] ^ P[r][3];
-      x = bs_bop3<kTtXorOr>(R[r][2], P[r][2], x);
-      x = bs_bop3<kTtXorOr>(R[r][1], P[r][1], x);
-      dh[r] = bs_bop3<kTtXorOr>(R[r][0], P[r][0], x);
-    } else {
-      dh[1] = dh[0];
-    }
+    if constexpr (CVD_BS_TREF_FAST == 0) dh[r] = (L5 != 5 || r == 0) ? bs_halves_diff(R[r], P[r]) : dh[0];
     if (r == 0) mid(N[0][3]);
   }
-  const bs_u32 sym = bs_bop3<kTtAndNotOr>(dh[0], e0[0], dh[1] & ~e0[1]);
-  c = 1u + (sym == 0u ? 1u : 0u) + ((kUni && (dh[0] | dh[1]) == 0u) ? 2u : 0u);
+  if constexpr (CVD_BS_TREF_FAST == 0) c = bs_tref_of(dh, e0, kUni);
+  if (all1) *all1 = one;
 }
 
 // The same step with mu's branch-metric planes from a table (CVD_BS_ETAB2): for each (phase,
@@ -441,7 +519,7 @@ CVD_HD void bs_add2(const bs_u32 (&d)[4], bs_u32 b0, bs_u32 b1, bs_u32 b23, bs_u
 // bs_step_core with e0 for the zero test and load(zero_hit) -> BsMu for the adds
 template <int PH, bool kUni, class Load, class Mid = BsNoMid>
 CVD_HD void bs_step_core_tab(const bs_u32 (&R)[2][4], const bs_u32 (&e0)[2], Load load, bs_u32 (&N)[2][4],
-                             bs_u32& mu, bs_u32& c, Mid mid = Mid()) {
+                             bs_u32& mu, bs_u32& c, Mid mid = Mid(), bool* all1 = nullptr) {
   constexpr int L5 = bs_sigma(PH, 5);
   bs_u32 z[2];
   for (int r = 0; r < 2; ++r) {
@@ -454,23 +532,19 @@ CVD_HD void bs_step_core_tab(const bs_u32 (&R)[2][4], const bs_u32 (&e0)[2], Loa
   bs_partner<PH>(R, P);
   const BsMu T = load(zero_hit);
   bs_u32 dh[2] = {0u, 0u};
+  bool one = false;
+  (void)dh; (void)L5;
+  if constexpr (CVD_BS_TREF_FAST != 0) bs_tref_count<PH, kUni>(R, P, e0, c, one);
   for (int r = 0; r < 2; ++r) {
     bs_u32 a[4], b[4];
     bs_add2(R[r], T.e0m[r], T.a1[r], T.a23[r], a);
     bs_add2(P[r], T.e0m[r], T.p1[r], T.p23[r], b);
     bs_min(a, b, N[r]);
-    if (L5 != 5 || r == 0) {
-      bs_u32 x = R[r][3] ^ P[r][3];
-      x = bs_bop3<kTtXorOr>(R[r][2], P[r][2], x);
-      x = bs_bop3<kTtXorOr>(R[r][1], P[r][1], x);
-      dh[r] = bs_bop3<kTtXorOr>(R[r][0], P[r][0], x);
-    } else {
-      dh[1] = dh[0];
-    }
+    if constexpr (CVD_BS_TREF_FAST == 0) dh[r] = (L5 != 5 || r == 0) ? bs_halves_diff(R[r], P[r]) : dh[0];
     if (r == 0) mid(N[0][3]);
   }
-  const bs_u32 sym = bs_bop3<kTtAndNotOr>(dh[0], e0[0], dh[1] & ~e0[1]);
-  c = 1u + (sym == 0u ? 1u : 0u) + ((kUni && (dh[0] | dh[1]) == 0u) ? 2u : 0u);
+  if constexpr (CVD_BS_TREF_FAST == 0) c = bs_tref_of(dh, e0, kUni);
+  if (all1) *all1 = one;
 }
 
 // the bit-sliced tables' key hash of the canonical digest (lo, hi): key_hash's two-word

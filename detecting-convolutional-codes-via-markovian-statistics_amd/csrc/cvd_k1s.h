@@ -196,9 +196,10 @@ __device__ __forceinline__ uint2 bs_e0_at(uint32_t rr) {
   const char* eb = reinterpret_cast<const char*>(bs_e0_lds()) + PH * 64;
   return *reinterpret_cast<const uint2*>(eb + word_off16(rr));
 }
+// (one, wave-uniform: no lane of the wave can have c > 1 -- cvd_bitslice.h CVD_BS_TREF_FAST)
 template <int PH, bool kUni, class Mid>
 __device__ __forceinline__ void bs_core_tab(const uint32_t (&R)[2][4], uint32_t rr, uint32_t (&N)[2][4], uint32_t& c,
-                                            Mid mid, const uint2* e0pre = nullptr) {
+                                            bool& one, Mid mid, const uint2* e0pre = nullptr) {
   // (CVD_BS_ETAB2=2: the lockstep loop read this step's e0 a step ahead, e0pre)
   const uint2 E0 = e0pre ? *e0pre : bs_e0_at<PH>(rr);
   const uint32_t e0[2] = {E0.x, E0.y};
@@ -217,7 +218,19 @@ __device__ __forceinline__ void bs_core_tab(const uint32_t (&R)[2][4], uint32_t 
         T.p23[0] = q.x; T.p23[1] = q.y;
         return T;
       },
-      N, mu, c, mid);
+      N, mu, c, mid, &one);
+}
+// lr += ltref[c]: the constant ltref[1] (lt1) where the step found no suspect lane in the wave
+// (one: c is then not set), without the LDS read
+// (the empty asm keeps the two adds apart: merged, the constant would be moved into the LDS
+// value's registers at every step)
+__device__ __forceinline__ void bs_lt_add(double& lr, const double* s_lt, double lt1, uint32_t c, bool one) {
+  if (__builtin_expect(one, 1)) {
+    lr += lt1;
+  } else {
+    lr += s_lt[c];
+    asm volatile("" : "+v"(lr));
+  }
 }
 
 // P̂1 row cursor over the bit-sliced tables (RowCursor's protocol: slot >= 0 known row id,
@@ -475,10 +488,10 @@ struct BsCursor {
 // the filter-positive loads issued between the two words' ACS
 template <int PH, bool kUni>
 __device__ __forceinline__ void bs_step(const ExpArgs& a, BsCursor& cur, const uint32_t (&R)[2][4], uint32_t rr,
-                                        uint32_t (&N)[2][4], uint32_t& c, const uint2* e0pre = nullptr) {
+                                        uint32_t (&N)[2][4], uint32_t& c, bool& one, const uint2* e0pre = nullptr) {
   if constexpr (CVD_BS_ETAB2 != 0) {
     static_assert(CVD_K1S_MIDPOS == 0, "CVD_BS_ETAB2 keeps the candidate test between the two words' ACS");
-    bs_core_tab<PH, kUni>(R, rr, N, c, [&](uint32_t dep) {
+    bs_core_tab<PH, kUni>(R, rr, N, c, one, [&](uint32_t dep) {
       cur.fence_mid(dep);            // dep: the first word's ACS result
       cur.template mid<PH>(a, rr);
     }, e0pre);
@@ -504,7 +517,7 @@ __device__ __forceinline__ void bs_step(const ExpArgs& a, BsCursor& cur, const u
       cur.fence_mid(dep);            // dep: the first word's ACS result
       cur.template mid<PH>(a, rr);
     }
-  });
+  }, &one);
   if constexpr (CVD_K1S_MIDPOS == 2) {
     cur.fence_mid(N[1][3]);
     cur.template mid<PH>(a, rr);
@@ -515,9 +528,10 @@ __device__ __forceinline__ void bs_step(const ExpArgs& a, BsCursor& cur, const u
 
 // the ACS of one step alone (the deep pipeline's lookups run after it)
 template <int PH, bool kUni>
-__device__ __forceinline__ void bs_acs(const uint32_t (&R)[2][4], uint32_t rr, uint32_t (&N)[2][4], uint32_t& c) {
+__device__ __forceinline__ void bs_acs(const uint32_t (&R)[2][4], uint32_t rr, uint32_t (&N)[2][4], uint32_t& c,
+                                       bool& one) {
   if constexpr (CVD_BS_ETAB2 != 0) {
-    bs_core_tab<PH, kUni>(R, rr, N, c, cvd::BsNoMid());
+    bs_core_tab<PH, kUni>(R, rr, N, c, one, cvd::BsNoMid());
     return;
   }
   const uint4* et = kR16 ? reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(bs_etab_lds()) + PH * 128 +
@@ -526,7 +540,7 @@ __device__ __forceinline__ void bs_acs(const uint32_t (&R)[2][4], uint32_t rr, u
   const uint4 E0 = et[0], E1 = et[1];
   const uint32_t e0[2] = {E0.x, E1.x}, e1[2] = {E0.y, E1.y}, ez[2] = {E0.z, E1.z};
   uint32_t mu;
-  cvd::bs_step_core<PH, kUni>(R, e0, e1, ez, N, mu, c);
+  cvd::bs_step_core<PH, kUni>(R, e0, e1, ez, N, mu, c, cvd::BsNoMid(), &one);
 }
 
 // Two-step lookup pipeline for the lockstep lanes (CVD_K1S_DEEP): every load of a lookup gets a
@@ -776,15 +790,17 @@ __device__ __forceinline__ void k1s_walk(const ExpArgs& a, int64_t qwave, uint64
     mode = kWalkWalk;
   }
   uint32_t phw = 0u;   // layout phase of the ACS lanes' planes (wave-uniform)
+  const double lt1 = a.ltref[1];
   // one ACS step of the wave at phase PH (every lane computes; ACS lanes keep the result)
   auto acs_step = [&](auto phc) {
     constexpr int PH = decltype(phc)::value;
     const uint32_t rr = word_param(word_at() & 3u);
     uint32_t Nn[2][4], c;
-    bs_step<PH, kUni>(a, cur, R, rr, Nn, c);
+    bool one;
+    bs_step<PH, kUni>(a, cur, R, rr, Nn, c, one);
     if (mode == kWalkAcs) {
       lp += cur.template resolve<PH>(a, R, rr, a.lp_unseen);   // Pd_plotter.py:115, T = P̂1
-      lr += s_lt[c];                                            // Pd_plotter.py:115, T = T_ref(1/2)
+      bs_lt_add(lr, s_lt, lt1, c, one);   // Pd_plotter.py:115, T = T_ref(1/2)
       advance();
       cur.template next<false>(a, 0u);
       if (finished()) {
@@ -1002,25 +1018,27 @@ __device__ __forceinline__ void k1s_wave(const ExpArgs& a, int64_t gw, const dou
     if (CVD_K1S_ABL & 1) cur.h2wave = hmask == 0u;
     // (CVD_BS_ETAB2=2: each step reads the next step's e0 from LDS, so the zero test does not
     // wait for it)
+    const double lt1 = a.ltref[1];   // (= s_lt[1]: the term of a wave-step without a suspect lane)
     uint2 e0c = make_uint2(0u, 0u);
     if constexpr (CVD_BS_ETAB2 == 2 && !kDeep) e0c = bs_e0_at<0>(word_param(cw & 3u));
     auto step = [&](auto phc, uint32_t rr, uint32_t rn, uint32_t rnn) {
       constexpr int PH = decltype(phc)::value;
       uint32_t Nn[2][4], c;
+      bool one;
       if constexpr (kDeep) {
-        bs_acs<PH, kUni>(R, rr, Nn, c);
+        bs_acs<PH, kUni>(R, rr, Nn, c, one);
         int32_t ns;
         if constexpr (CVD_K1S_DEEP == 2) {
           const typename BsDeep::Prep h = cur.template prep<(PH + 1) % 6>(a, Nn);
           cur.fence_all(Nn, h.fo, h.fb1);
           lp += cur.template resolve_a<(PH + 5) % 6>(a, Rp, lpu, ns);   // Pd_plotter.py:115, T = P̂1 (step t - 1)
-          lr += s_lt[c];                                                // Pd_plotter.py:115, T = T_ref(1/2)
+          bs_lt_add(lr, s_lt, lt1, c, one);   // Pd_plotter.py:115, T = T_ref(1/2)
           cur.template mid_b<PH>(a, ns, rr);
           cur.issue(a, h);
         } else {
           cur.fence_all(Nn);
           lp += cur.template resolve_a<(PH + 5) % 6>(a, Rp, lpu, ns);   // Pd_plotter.py:115, T = P̂1 (step t - 1)
-          lr += s_lt[c];                                                // Pd_plotter.py:115, T = T_ref(1/2)
+          bs_lt_add(lr, s_lt, lt1, c, one);   // Pd_plotter.py:115, T = T_ref(1/2)
           cur.template mid_b<PH>(a, ns, rr);
           cur.template hash_ahead<(PH + 1) % 6>(a, Nn);
         }
@@ -1032,9 +1050,9 @@ __device__ __forceinline__ void k1s_wave(const ExpArgs& a, int64_t gw, const dou
         if constexpr (CVD_BS_ETAB2 == 2) {
           const uint2 e0u = e0c;
           e0c = bs_e0_at<(PH + 1) % 6>(rn);   // the next step's (its word rn, its phase)
-          bs_step<PH, kUni>(a, cur, R, rr, Nn, c, &e0u);
+          bs_step<PH, kUni>(a, cur, R, rr, Nn, c, one, &e0u);
         } else {
-          bs_step<PH, kUni>(a, cur, R, rr, Nn, c);
+          bs_step<PH, kUni>(a, cur, R, rr, Nn, c, one);
         }
 #if CVD_K1S_PADV
         {   // (timing ablation, sums unchanged: CVD_K1S_PADV independent v_bitop3 per step, two chains)
@@ -1048,7 +1066,7 @@ __device__ __forceinline__ void k1s_wave(const ExpArgs& a, int64_t gw, const dou
         }
 #endif
         lp += cur.template resolve<PH>(a, R, rr, lpu);   // Pd_plotter.py:115, T = P̂1
-        lr += s_lt[c];                                   // Pd_plotter.py:115, T = T_ref(1/2) = c / 2^n
+        bs_lt_add(lr, s_lt, lt1, c, one);               // Pd_plotter.py:115, T = T_ref(1/2) = c / 2^n
       }
 #pragma unroll
       for (int r = 0; r < 2; ++r)
