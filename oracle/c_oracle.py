@@ -37,6 +37,8 @@ def lib():
         L.oc_run_trials.argtypes = [ctypes.c_void_p, ctypes.POINTER(oc_code), ctypes.POINTER(oc_code),
                                     ctypes.c_int64, ctypes.c_double, ctypes.c_uint64, ctypes.c_int64,
                                     ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
+        L.oc_score_words.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
+                                     ctypes.c_void_p, ctypes.c_void_p]
         L.oc_stream.argtypes = [ctypes.POINTER(oc_code), ctypes.c_int64, ctypes.c_double,
                                 ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_void_p]
         L.oc_grid_tag.restype = ctypes.c_uint32
@@ -85,6 +87,21 @@ class Model:
         lib().oc_run_trials(self.h, ctypes.byref(enc1.c), ctypes.byref(enc2.c), N, p, seed, t0, t1,
                             out.ctypes.data if sums else None, counts.ctypes.data, nthreads)
         return counts, out
+
+    def score_words(self, words):
+        """(sums [nseq, 2] = (log P1, log T_ref), stats [nseq, 4]) of received words [nseq, N]
+        given by the caller: the per-sequence loop of run_trials (oc_score_words).  stats =
+        steps whose D_{t-1} was a learned row, re-entries (not a row, then a row), steps with
+        c > 1, steps with c > 1 at t > 0."""
+        w = np.ascontiguousarray(words, dtype=np.int32)
+        if w.ndim != 2:
+            raise ValueError("words is [nseq, N]")
+        nseq, N = w.shape
+        sums = np.zeros((nseq, 2))
+        stats = np.zeros((nseq, 4), np.int64)
+        if lib().oc_score_words(self.h, w.ctypes.data, N, nseq, sums.ctypes.data, stats.ctypes.data) != 0:
+            raise ValueError("a word outside [0, 2^n)")
+        return sums, stats
 
     def __del__(self):
         if getattr(self, "h", None):

@@ -14,6 +14,7 @@
  *   oc_stream            the missing simulate_markov_sequence (build spec, oracle/philox.py)
  *   oc_log_prob          Pd_plotter.py:106-116     log_prob_sequence
  *   oc_run_trials        Pd_plotter.py:198-233     trial loop + decisions
+ *   oc_score_words       Pd_plotter.py:106-116     the same sums over a caller's words
  * The state index is a hash map keyed by the full metric vector, exactly the
  * reference's dict (Pd_plotter.py:139); rows are Laplace-smoothed count rows.
  * Row sums use the closed form R_i + S*laplace, equal to numpy's pairwise sum
@@ -332,33 +333,70 @@ void oc_model_destroy(void* m) {
 }
 
 /* ───────────────────────── one sequence (Pd:106-116) ─────────────────────── */
-static void oc_sequence(const Model* Mo, const Tabs* Te, int64_t N, double p, uint64_t seed, uint32_t tag,
-                        uint64_t sid, double* lp_out, double* lr_out) {
+/* One step of log_prob_sequence: received word r at D = D_{t-1}; adds log P1 and
+ * log T_ref to *lp / *lr, steps D, returns c = |Y(i,j)|; *row = D was a learned row. */
+static int oc_seq_step(const Model* Mo, uint8_t* D, int r, double* lp, double* lr, int* row) {
   const Tabs* T = &Mo->T;
   const int M = T->M, R = T->R;
+  uint8_t succ[16][256];
+  const int64_t i = idx_find(&Mo->idx, D);          /* state_index[metrics[t]] */
+  int c = 0;
+  if (Mo->kind == 0) {
+    oc_step(T, D, r, succ[r]);
+    c = Mo->cnt_c[i * R + r];                        /* |Y(i,j)| */
+  } else {
+    for (int q = 0; q < R; ++q) oc_step(T, D, q, succ[q]);
+    for (int q = 0; q < R; ++q) c += !memcmp(succ[q], succ[r], (size_t)M);
+  }
+  const double pij = i >= 0 ? Mo->logp1[i * R + r] : Mo->unseen;
+  const double tij = (double)c / (double)R;
+  *lp += pij;
+  *lr += log(tij > 1e-300 ? tij : 1e-300);
+  memcpy(D, succ[r], (size_t)M);
+  *row = i >= 0;
+  return c;
+}
+
+static void oc_sequence(const Model* Mo, const Tabs* Te, int64_t N, double p, uint64_t seed, uint32_t tag,
+                        uint64_t sid, double* lp_out, double* lr_out) {
   Stream st;
   stream_init(&st, Te, seed, tag, sid, p);
-  uint8_t D[256] = {0}, succ[16][256];
+  uint8_t D[256] = {0};
   double lp = 0.0, lr = 0.0;
-  for (int64_t t = 0; t < N; ++t) {
-    const int r = stream_next(&st, t);
-    const int64_t i = idx_find(&Mo->idx, D);          /* state_index[metrics[t]] */
-    int c = 0;
-    if (Mo->kind == 0) {
-      oc_step(T, D, r, succ[r]);
-      c = Mo->cnt_c[i * R + r];                        /* |Y(i,j)| */
-    } else {
-      for (int q = 0; q < R; ++q) oc_step(T, D, q, succ[q]);
-      for (int q = 0; q < R; ++q) c += !memcmp(succ[q], succ[r], (size_t)M);
-    }
-    const double pij = i >= 0 ? Mo->logp1[i * R + r] : Mo->unseen;
-    const double tij = (double)c / (double)R;
-    lp += pij;
-    lr += log(tij > 1e-300 ? tij : 1e-300);
-    memcpy(D, succ[r], (size_t)M);
-  }
+  int row;
+  for (int64_t t = 0; t < N; ++t) oc_seq_step(Mo, D, stream_next(&st, t), &lp, &lr, &row);
   *lp_out = lp;
   *lr_out = lr;
+}
+
+/* The loop of oc_sequence over the caller's words[nseq][N] (each in [0, 2^n)) instead of
+ * the simulator's: sums[nseq][2] = (log P1, log T_ref); stats[nseq][4] (nullable) = steps
+ * whose D_{t-1} was a learned row, re-entries (not a row, then a row), steps with c > 1,
+ * steps with c > 1 at t > 0.  Returns -1 on a word outside [0, 2^n). */
+int oc_score_words(void* model, const int32_t* words, int64_t N, int64_t nseq, double* sums, int64_t* stats) {
+  const Model* Mo = model;
+  for (int64_t x = 0; x < nseq * N; ++x)
+    if (words[x] < 0 || words[x] >= Mo->T.R) return -1;
+#ifdef _OPENMP
+#pragma omp parallel for schedule(dynamic, 1)
+#endif
+  for (int64_t q = 0; q < nseq; ++q) {
+    uint8_t D[256] = {0};
+    double lp = 0.0, lr = 0.0;
+    int64_t st[4] = {0, 0, 0, 0};
+    int row, prev = 1;
+    for (int64_t t = 0; t < N; ++t) {
+      const int c = oc_seq_step(Mo, D, words[q * N + t], &lp, &lr, &row);
+      st[0] += row;
+      st[1] += row && !prev;
+      st[2] += c > 1;
+      st[3] += c > 1 && t > 0;
+      prev = row;
+    }
+    sums[2 * q] = lp; sums[2 * q + 1] = lr;
+    if (stats) memcpy(stats + 4 * q, st, sizeof st);
+  }
+  return 0;
 }
 
 /* Trials [t0, t1) of one (N, p) grid point; sums [T][4] (nullable), counts[2]. */

@@ -7,9 +7,12 @@ returns no sums) and detect_multi -- and identical to the knob-off build's, whic
 exactly in every lane at every step.
 
 Shape: the m = 6 pair, N = 768 (128 six-step groups), 256 trials = 512 sequences, so every
-wave is all-H1 or all-H2; the first steps from D_0 = 0 have c > 1 in every sequence (the exact
-path), the rest almost never.  p = 0.01 / 0.05 / 0.2: the LDS-filter, the pre-filter and the
-plain-filter variants of the kernel."""
+wave is all-H1 or all-H2; step 0 alone, from D_0 = 0, has c > 1 (c = 2) in every sequence (the
+exact path with a count above 1).  Of the 3 * 512 * 767 later steps the oracle counts c > 1 at
+one (p = 0.2, an H2 sequence; tests/test_oracle_score_host.py asserts it): there the exact path is entered only for suspects whose count
+turns out to be 1, and the g1 = g2 (kUni, c = 4) instantiations never run here
+(tests/test_gpu_foreign_streams.py has both).  p = 0.01 / 0.05 / 0.2: the LDS-filter, the
+pre-filter and the plain-filter variants of the kernel."""
 import numpy as np
 import pytest
 import torch
