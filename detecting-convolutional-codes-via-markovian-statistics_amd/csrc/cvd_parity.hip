@@ -23,7 +23,7 @@
 namespace {
 
 constexpr int kBlock = 256;
-constexpr int kMaxTerms = 32;   // per output stream (n = 3) / in total (n <= 2)
+constexpr int kMaxTerms = 32;   // per output stream (n = 3) / per word pair (n <= 2)
 constexpr int kMaxOut = 3;
 
 struct ParArgs {
@@ -167,7 +167,8 @@ extern "C" int cvd_parity_detect(const uint32_t* d_r, int32_t n, int64_t N, int6
     const int tj = terms[2 * e], ts = terms[2 * e + 1];
     const int smax = n <= 2 ? (64 + tj) / n : 64 - spw;   // n <= 2: o = n*s - j <= 64
     if (tj < 0 || tj >= n || ts < 0 || ts > smax) {
-      cvd::set_error("parity_detect: term (j, s) needs 0 <= j < n and n*s - j <= 64 (n <= 2) / s <= 54 (n = 3)");
+      cvd::set_error("parity_detect: term (j, s) needs 0 <= j < n, s >= 0 and n*s - j <= 64 (n <= 2) / "
+                     "s <= 54 (n = 3)");
       return CVD_E_INVALID;
     }
     first = std::max<int64_t>(first, ts);
@@ -176,16 +177,26 @@ extern "C" int cvd_parity_detect(const uint32_t* d_r, int32_t n, int64_t N, int6
       const int g = o <= 0 ? 2 : o <= 32 ? 0 : 1;
       const uint32_t sh = o <= 0 ? (uint32_t)(-o) : o <= 32 ? (uint32_t)(32 - o) : (uint32_t)(64 - o);
       int& c = a.cnt[g];
-      if (c >= kMaxTerms) { cvd::set_error("parity_detect: more than 32 terms per word pair"); return CVD_E_INVALID; }
+      if (c >= kMaxTerms) {
+        cvd::set_error("parity_detect: more than 32 terms with 1 <= n*s - j <= 32, or with 33 <= n*s - j <= 64");
+        return CVD_E_INVALID;
+      }
       a.mk[g][c] = ~0u;
       a.sh[g][c++] = sh;
     } else {
       int& c = a.cnt[tj];
-      if (c >= kMaxTerms) { cvd::set_error("parity_detect: more than 32 terms per output"); return CVD_E_INVALID; }
+      if (c >= kMaxTerms) {
+        cvd::set_error("parity_detect: more than 32 terms per output (n = 3)");
+        return CVD_E_INVALID;
+      }
       a.sh[tj][c++] = (uint32_t)(64 - spw - ts);
     }
   }
   a.first = first;
+  if (n <= 2 && a.cnt[2] > 2) {
+    cvd::set_error("parity_detect: more than two terms with n*s - j <= 0");
+    return CVD_E_INVALID;
+  }
   if (nseq == 0) return CVD_OK;
   const unsigned grid = (unsigned)((nseq + kBlock - 1) / kBlock);
   void (*kern)(ParArgs) = parity_kernel<3>;
@@ -204,7 +215,6 @@ extern "C" int cvd_parity_detect(const uint32_t* d_r, int32_t n, int64_t N, int6
                                 parity_kernel<2, 32, 32, 2>}};
     const int i0 = T0 == 4 ? 0 : T0 == 8 ? 1 : T0 == 16 ? 2 : 3;
     kern = (n == 1 ? k1 : k2)[c1 > 0 ? 1 : 0][i0];
-    if (a.cnt[2] > 2) { cvd::set_error("parity_detect: duplicate terms"); return CVD_E_INVALID; }
   }
   hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, a);
   HIP_CHECK(hipGetLastError());

@@ -386,8 +386,18 @@ void cvd_comm_destroy(cvd_comm* comm);
  * template's largest delay max_s), P̂ = sat / (N - max_s), 0.0 without anchors.
  * Sequences q < n_h1 succeed iff P̂ >= gamma (decide H1), the rest iff P̂ < gamma
  * (comp_parity.py:120-128); d_counts[2] accumulated as in cvd_detect.
- * terms: [n_terms][2] (output j, delay s), 1 <= n <= 3, 1 <= n_terms <= 64,
- * 0 <= s <= 64 - floor(32/n).  d_sat (nullable): [nseq] int32 satisfied counts. */
+ * terms: [n_terms][2] (output j, delay s), 1 <= n <= 3, 1 <= n_terms <= 96, every term
+ * with 0 <= j < n and s >= 0.  A term lies o = n*s - j stream bits behind its anchor's
+ * bit, and the kernel keeps 64 bits of history:
+ *   n <= 2: o <= 64 (n = 1: s <= 64; n = 2: s <= 32).  The terms fall in three groups by
+ *           the word pair they are read from: o <= 0 (the anchor's own word: (0, 0), and
+ *           (1, 0) for n = 2), 1 <= o <= 32, and 33 <= o <= 64.  A third term with o <= 0
+ *           and a 33rd term in either of the other groups are refused (only a template
+ *           with repeated terms can have them).
+ *   n = 3:  s <= 54, and at most 32 terms per output.
+ * Repeated terms that pass these limits cancel in the XOR, as in the reference; max_s is
+ * over all terms given.  CVD_E_INVALID, without a launch, for anything outside these
+ * limits.  d_sat (nullable): [nseq] int32 satisfied counts. */
 int cvd_parity_detect(const uint32_t* d_r, int32_t n, int64_t N, int64_t nseq, int64_t n_h1,
                       const int32_t* terms, int32_t n_terms, double gamma, int32_t* d_sat,
                       int64_t* d_counts, void* stream);
