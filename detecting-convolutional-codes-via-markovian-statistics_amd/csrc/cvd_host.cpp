@@ -1250,7 +1250,10 @@ extern "C" int cvd_model_create_device(const cvd_code* dec, const cvd_learn_para
 // fresh box then loads them instead of compiling ~10 s per variant at model upload.  The
 // bit-sliced codes' (m = 6) lockstep variant (pre-filter, 1,024-thread blocks) and the walking
 // models' LDS-filter variants (1,024 and 512 threads).
-extern "C" int cvd_jit_prebuild(const cvd_code* dec, const char* arch, const char* dir, int32_t* n_built) {
+// (the bit-sliced kernel does not walk by default, so the variants a model gets at upload are
+// the ones without walk mode, kNoWalkDef; `walk`: the same three with it, which a launch under
+// CVD_WALK=1 asks for -- cvd_jit_prebuild_walk)
+static int jit_prebuild(const cvd_code* dec, const char* arch, const char* dir, int32_t* n_built, bool walk) {
   CVD_TRY
   if (!dec || !arch || !dir || !n_built) { set_error("null argument"); return CVD_E_INVALID; }
   *n_built = 0;
@@ -1260,10 +1263,11 @@ extern "C" int cvd_jit_prebuild(const cvd_code* dec, const char* arch, const cha
   const Tabs T = make_tabs(Mo.dec);
   build_bmp(Mo, T);
   if (!Mo.k1b_ok || !bitslice_preferred(Mo)) return CVD_OK;   // (only the bit-sliced codes)
+  const std::string nw = walk ? "" : kNoWalkDef;
   const std::string vs[] = {
-      rtc_variant_defs(kBsPfLog2Bits >= 20 ? 1024 : 512, false, kFilterPatBitsLds, true, true, kBsPfLog2Bits),
-      rtc_variant_defs(1024, true, kFilterPatBitsLds, true, false, kBsPfLog2Bits),
-      rtc_variant_defs(512, true, kFilterPatBitsLds, true, false, kBsPfLog2Bits)};
+      rtc_variant_defs(kBsPfLog2Bits >= 20 ? 1024 : 512, false, kFilterPatBitsLds, true, true, kBsPfLog2Bits) + nw,
+      rtc_variant_defs(1024, true, kFilterPatBitsLds, true, false, kBsPfLog2Bits) + nw,
+      rtc_variant_defs(512, true, kFilterPatBitsLds, true, false, kBsPfLog2Bits) + nw};
   std::vector<std::thread> th;
   std::vector<int> res(3, 0);
   std::vector<std::string> errs(3);
@@ -1279,6 +1283,12 @@ extern "C" int cvd_jit_prebuild(const cvd_code* dec, const char* arch, const cha
   }
   return CVD_OK;
   CVD_CATCH
+}
+extern "C" int cvd_jit_prebuild(const cvd_code* dec, const char* arch, const char* dir, int32_t* n_built) {
+  return jit_prebuild(dec, arch, dir, n_built, false);
+}
+extern "C" int cvd_jit_prebuild_walk(const cvd_code* dec, const char* arch, const char* dir, int32_t* n_built) {
+  return jit_prebuild(dec, arch, dir, n_built, true);
 }
 
 extern "C" int cvd_model_info_get(const cvd_model* Mo, cvd_model_info* info) {

@@ -101,6 +101,13 @@ struct cvd_model {
   bool rtc_ldsf = false;           // it reads the Bloom filter from dynamic LDS (fcap * 4 bytes)
   bool rtc_pf = false;             // it tests the LDS pre-filter h_bpf before the L2 filter (k1s)
   int64_t rtc_persist_grid = 0;    // k1s: blocks of a persistent (work-queue) launch, 0 = none
+  // k1s built without walk mode (-DCVD_K1S_WALK=0, the default for a model that does not walk:
+  // the lockstep loop alone needs fewer registers): a launch that is to walk after all
+  // (CVD_WALK=1) runs the walking variant `rtc_walk_defs`, built on first use (walk_functions)
+  bool rtc_nowalk = false;
+  std::string rtc_walk_defs;
+  mutable void* rtc_fn_walk = nullptr;
+  mutable void* rtc_fn_multi_walk = nullptr;
   std::string jit_error;           // why the specialised kernel is unavailable (empty if built or n/a)
   std::vector<uint32_t> bfly;      // [2^m / 2]
 
@@ -190,6 +197,8 @@ int rtc_k1b_function(int device, int m, uint64_t xm, const char* variant_defs, v
 // the -D set of a specialised-kernel variant (upload_model, and cvd_jit_prebuild: the same text
 // keys the same code object)
 std::string rtc_variant_defs(int block, bool ldsf, int patbits, bool bs, bool pf, int pf_log2, bool slot3 = false);
+// appended to it for k1s without walk mode (cvd_model::rtc_nowalk)
+constexpr const char* kNoWalkDef = " -DCVD_K1S_WALK=0";
 // compile one variant for `arch` into `dir` (the prebuilt cache rtc_k1b_function reads first);
 // 0 = ok (or already there)
 int rtc_prebuild(int m, uint64_t xm, const char* variant_defs, const char* arch, const char* dir);

@@ -93,6 +93,28 @@ constexpr bool kK1sT2 = CVD_K1S_T2 != 0;
 #ifndef CVD_K1S_CK
 #define CVD_K1S_CK 1
 #endif
+// Walk mode (k1s_walk) compiled in (default) or out (-DCVD_K1S_WALK=0; the host then must not set
+// a.walk: cvd_kernels.hip builds the walking variant on first use).  A kernel's VGPR count is
+// the largest over all its code, and walk mode's is the larger one: with the pre-filter 115
+// against the lockstep loop's 90, so the kernel that only runs the lockstep loop is allocated
+// 104 registers per lane (CVD_K1B_ENTRY_ATTR below) instead of 120 and its four waves leave 96
+// of a SIMD's 512 to a co-resident kernel -- a generator wave -- instead of 32 (DESIGN.md §7.1,
+// register budget)
+#ifndef CVD_K1S_WALK
+#define CVD_K1S_WALK 1
+#endif
+// The entries' occupancy attribute (cvd_rtc.cpp entry_source, spec_resource.py).  By its ~90
+// registers alone the kernel without walk mode would hold five waves per SIMD, and the compiler
+// then schedules for five; its blocks never hold more than CVD_K1B_WAVES (1,024 threads around
+// 128 KiB of LDS, or 256 threads with 35 KiB).  Told so, the compiler gives the six-step loop the
+// schedule it has in the walking build (32 s_waitcnt instead of 40, the same 90 registers):
+// without the attribute the lockstep launches alone measured 0.2-1.2% longer than the walking
+// build's (profiles/coresident/ab.json, overlap_0).  The walking build is compiled as before.
+#if CVD_K1B_BITSLICE && !CVD_K1S_WALK
+#define CVD_K1B_ENTRY_ATTR __attribute__((amdgpu_waves_per_eu(CVD_K1B_WAVES, CVD_K1B_WAVES)))
+#else
+#define CVD_K1B_ENTRY_ATTR
+#endif
 // Word offsets (CVD_K1S_R16, default on): a step's received words enter the cursor and the
 // branch-metric table as byte offsets 16 r, each one v_lshrrev and one v_and of the six-step
 // group's window shifted once -- both take vector or constant operands at ~2.5 cycles per
@@ -960,9 +982,11 @@ __device__ __forceinline__ void k1s_wave(const ExpArgs& a, int64_t gw, const dou
   const int64_t q = qwave + lane_id();
   const bool valid = q < a.nseq;
   const uint64_t vmask = __ballot(valid), hmask = __ballot(q < a.n_h1);
-  if (a.walk && vmask != 0u && hmask == vmask) {
-    k1s_walk<XM>(a, qwave, vmask, s_lt);
-    return;
+  if constexpr (CVD_K1S_WALK != 0) {
+    if (a.walk && vmask != 0u && hmask == vmask) {
+      k1s_walk<XM>(a, qwave, vmask, s_lt);
+      return;
+    }
   }
   // (timing ablation, CVD_WALK_ABL & 4: a walk launch's lockstep (H2) waves do nothing)
   if ((CVD_WALK_ABL & 4) && a.walk) return;

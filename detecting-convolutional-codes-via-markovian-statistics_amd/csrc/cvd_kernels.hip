@@ -20,6 +20,9 @@
 #include <algorithm>
 #include <atomic>
 #include <cstdlib>
+#include <cstring>
+#include <map>
+#include <mutex>
 #include <string>
 
 #include "../../include/cvd.h"
@@ -737,7 +740,10 @@ struct ChunkEncoder {
   }
 };
 
-template <int k, int n, int kT>
+// kVK: the noise keys' round keys in VGPRs (the fast form, 80 VGPRs for k = 1, n = 2), or as
+// the launch's SGPR pair (the small form, <= 64 VGPRs: one wave of it fits beside the m = 6
+// detector's four waves on a SIMD -- launch_generate chooses); same streams
+template <int k, int n, int kT, bool kVK = CVD_GEN_VKEYS != 0>
 __global__ __launch_bounds__(kBlock) void gen_fast_kernel(GenArgs a) {
   constexpr int SPW = 32 / n;
   static_assert(k >= 1 && k <= 2 && SPW * k <= 32, "gen_fast_kernel: shape");
@@ -773,7 +779,7 @@ __global__ __launch_bounds__(kBlock) void gen_fast_kernel(GenArgs a) {
 #endif
   const int64_t nwords = (a.N + SPW - 1) / SPW;
   const int64_t nw4 = (nwords + 3) & ~(int64_t)3;
-  ChunkEncoder<k, n, kT, CVD_GEN_VKEYS != 0> enc;
+  ChunkEncoder<k, n, kT, kVK> enc;
   enc.init(&a, sid);
   // segment blockIdx.y of the sequence's 16-byte chunks: every word depends only
   // on its own inputs and the hs input steps before it, so segments are
@@ -1669,9 +1675,86 @@ int tap_slots(int ntap) {
   return 0;
 }
 
+// The persistent m = 6 detector launch last enqueued on each device (launch_detect_explicit): the
+// stream it went to and an event recorded behind it.  launch_generate asks whether that launch
+// is still pending and on another stream than the generator's -- the one case in which the two
+// kernels run side by side -- and then takes the generator form whose waves fit beside the
+// detector's (gen_small_form).
+struct PersistMark {
+  hipEvent_t ev = nullptr;
+  hipStream_t stream = nullptr;
+  bool set = false;
+};
+std::mutex g_persist_mu;
+std::map<int, PersistMark> g_persist;
+
+void persist_mark(hipStream_t stream) {
+  int dev = 0;
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  if (hipGetDevice(&dev) != hipSuccess) return;
+  // (a capturing stream records nothing that can be queried: the mark is left as it was)
+  if (hipStreamIsCapturing(stream, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) return;
+  std::lock_guard<std::mutex> lock(g_persist_mu);
+  PersistMark& m = g_persist[dev];
+  if (!m.ev && hipEventCreateWithFlags(&m.ev, hipEventDisableTiming) != hipSuccess) {
+    m.ev = nullptr;
+    return;
+  }
+  m.set = hipEventRecord(m.ev, stream) == hipSuccess;
+  m.stream = stream;
+}
+
+// a persistent detector launch is pending on this device, on another stream than `stream`
+bool persist_beside(hipStream_t stream) {
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return false;
+  // (a generator launch that is being captured into a graph runs later, beside whatever: no query)
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(stream, &cap) != hipSuccess) {
+    (void)hipGetLastError();
+    return false;
+  }
+  if (cap != hipStreamCaptureStatusNone) return false;
+  std::lock_guard<std::mutex> lock(g_persist_mu);
+  auto it = g_persist.find(dev);
+  if (it == g_persist.end() || !it->second.set || it->second.stream == stream) return false;
+  const hipError_t q = hipEventQuery(it->second.ev);
+  if (q != hipErrorNotReady) {
+    if (q != hipSuccess) (void)hipGetLastError();
+    it->second.set = false;   // done (or not to be had): nothing runs beside the next generator
+    return false;
+  }
+  return true;
+}
+
+// The k = 1, n = 2 generator's form for this launch: 1 the small one (round keys as SGPR
+// operands, <= 64 VGPRs), 0 the fast one (round keys in VGPRs, 80).  CVD_GEN_FORM=small / fast
+// forces one (A/Bs, tests); the default is the small form exactly where a persistent detector
+// launch is pending on another stream: its four waves per SIMD leave 96 registers, one wave of
+// either form, and the small one measured level or slightly ahead there and still fits should
+// the detector grow to 112.  Alone the small form is ~5% slower, so every
+// other launch keeps the fast one.
+bool gen_small_form(hipStream_t stream) {
+  if (const char* e = std::getenv("CVD_GEN_FORM")) {
+    if (!std::strcmp(e, "small")) return true;
+    if (!std::strcmp(e, "fast")) return false;
+  }
+  return persist_beside(stream);
+}
+
 template <int k, int n>
-void (*gen_fast_variant(int kt))(GenArgs) {
+void (*gen_fast_variant(int kt, bool small = false))(GenArgs) {
   if constexpr (k == 2 && !CVD_GEN_K2_STRIDE3) return gen_fast_kernel<k, n, 0>;
+  if constexpr (k == 1 && n == 2 && CVD_GEN_VKEYS != 0) {
+    if (small) switch (kt) {
+      case 3: return gen_fast_kernel<k, n, 3, false>;
+      case 4: return gen_fast_kernel<k, n, 4, false>;
+      case 5: return gen_fast_kernel<k, n, 5, false>;
+      case 6: return gen_fast_kernel<k, n, 6, false>;
+      case 8: return gen_fast_kernel<k, n, 8, false>;
+      default: return gen_fast_kernel<k, n, 0, false>;
+    }
+  }
   switch (kt) {
     case 3: return gen_fast_kernel<k, n, 3>;
     case 4: return gen_fast_kernel<k, n, 4>;
@@ -1702,7 +1785,7 @@ int cvd::launch_generate(const CodeDesc& enc, uint32_t k0, uint32_t k1, uint32_t
     gdim.y = (unsigned)std::min<int64_t>(seg, 65535);
   }
   const int kt = tap_slots(a.ntap);
-  if (fast && enc.k == 1 && enc.n == 2) kern = gen_fast_variant<1, 2>(kt);
+  if (fast && enc.k == 1 && enc.n == 2) kern = gen_fast_variant<1, 2>(kt, gen_small_form((hipStream_t)stream));
   else if (fast && enc.k == 1 && enc.n == 3) kern = gen_fast_variant<1, 3>(kt);
   else if (fast && enc.k == 2 && enc.n == 3) kern = gen_fast_variant<2, 3>(kt);
   else if (enc.k == 1 && enc.n == 2) kern = gen_kernel<1, 2>;
@@ -2007,6 +2090,29 @@ static ExpArgs exp_args(const cvd_model& M, int which, const uint32_t* d_r, int6
   return a;
 }
 
+// The specialised kernel's entries for a launch that walks (`walk`) or not: the model's own, or
+// -- a model whose k1s was built without walk mode (rtc_nowalk) -- the walking variant, compiled
+// or loaded from the JIT caches on first use.  A walking variant that cannot be built is an error.
+static int rtc_entries(const cvd_model& M, bool walk, void** fn, void** fn_multi) {
+  *fn = M.rtc_fn;
+  if (fn_multi) *fn_multi = M.rtc_fn_multi;
+  if (!walk || !M.rtc_nowalk) return CVD_OK;
+  static std::mutex mu;
+  std::lock_guard<std::mutex> lock(mu);
+  if (!M.rtc_fn_walk &&
+      rtc_k1b_function(M.device, M.dec.m, M.bfly_x, M.rtc_walk_defs.c_str(), &M.rtc_fn_walk, &M.rtc_fn_multi_walk) != 0) {
+    M.rtc_fn_walk = nullptr;
+    M.rtc_fn_multi_walk = nullptr;
+    return CVD_E_UNSUPPORTED;   // (rtc_k1b_function set the error text)
+  }
+  *fn = M.rtc_fn_walk;
+  if (fn_multi) {
+    if (!M.rtc_fn_multi_walk) { set_error("walking variant without the multi-model entry"); return CVD_E_UNSUPPORTED; }
+    *fn_multi = M.rtc_fn_multi_walk;
+  }
+  return CVD_OK;
+}
+
 int cvd::launch_detect_explicit(const cvd_model& M, const uint32_t* d_r, int64_t N, int64_t nseq,
                                 int64_t n_h1, double* d_sums, int64_t* d_counts, uint8_t* d_trace,
                                 void* stream, int variant, bool early) {
@@ -2022,6 +2128,8 @@ int cvd::launch_detect_explicit(const cvd_model& M, const uint32_t* d_r, int64_t
   const unsigned grid = (unsigned)((nseq + kBlock - 1) / kBlock);
   if (which == CVD_KERNEL_BUTTERFLY_RTC) {
     void* args[] = {&a};
+    void* fn = nullptr;
+    if (const int rc = rtc_entries(M, a.walk != 0, &fn, nullptr)) return rc;
     const unsigned blk = (unsigned)M.rtc_block;
     unsigned rgrid = (unsigned)((nseq + blk - 1) / blk);
     const unsigned lds = rtc_dyn_lds(M);   // the filter (CVD_K1B_LDSF) or the pre-filter (CVD_K1S_PF)
@@ -2035,9 +2143,12 @@ int cvd::launch_detect_explicit(const cvd_model& M, const uint32_t* d_r, int64_t
       HIP_CHECK(hipMemsetAsync(a.wq, 0, sizeof(uint32_t), (hipStream_t)stream));
       rgrid = (unsigned)pgrid;
     }
-    HIP_CHECK(hipModuleLaunchKernel((hipFunction_t)M.rtc_fn, rgrid, 1, 1, blk, 1, 1, lds,
+    HIP_CHECK(hipModuleLaunchKernel((hipFunction_t)fn, rgrid, 1, 1, blk, 1, 1, lds,
                                     (hipStream_t)stream, args, nullptr));
-    if (a.wq) HIP_CHECK(hipFreeAsync(a.wq, (hipStream_t)stream));
+    if (a.wq) {
+      HIP_CHECK(hipFreeAsync(a.wq, (hipStream_t)stream));
+      if (M.rtc_bs) persist_mark((hipStream_t)stream);   // (launch_generate: the generator form beside it)
+    }
     return CVD_OK;
   }
   hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, a);
@@ -2070,7 +2181,11 @@ static int launch_multi(const cvd_model* const* models, int32_t i0, int32_t i1, 
   for (int j = ma.nm; j < kMultiMax; ++j) ma.blk_end[j] = blocks;
   void* args[] = {&ma};
   const unsigned lds = rtc_dyn_lds(M0);
-  HIP_CHECK(hipModuleLaunchKernel((hipFunction_t)M0.rtc_fn_multi, blocks, 1, 1, blk, 1, 1, lds, (hipStream_t)stream,
+  bool walks = false;
+  for (int j = 0; j < ma.nm; ++j) walks = walks || ma.a[j].walk != 0;
+  void *fn = nullptr, *fnm = nullptr;
+  if (const int rc = rtc_entries(M0, walks, &fn, &fnm)) return rc;
+  HIP_CHECK(hipModuleLaunchKernel((hipFunction_t)fnm, blocks, 1, 1, blk, 1, 1, lds, (hipStream_t)stream,
                                   args, nullptr));
   return CVD_OK;
 }
@@ -2321,6 +2436,9 @@ int cvd::upload_model(cvd_model& M, int device) {
   // cvd_model_jit_status
   M.rtc_fn = nullptr;
   M.rtc_fn_multi = nullptr;
+  M.rtc_fn_walk = nullptr;
+  M.rtc_fn_multi_walk = nullptr;
+  M.rtc_nowalk = false;
   M.jit_error.clear();
   M.rtc_ldsf = M.k1b_ok && M.hcap > 0 && ldsf_preferred(M);
   // the bit-sliced form (k1s) for models with the bit-sliced tables, with the LDS pre-filter
@@ -2336,10 +2454,16 @@ int cvd::upload_model(cvd_model& M, int device) {
     M.rtc_block = pf ? (M.bs_pf_log2 >= 20 ? 1024 : 512) : env_i("CVD_K1B_BLOCK", M.rtc_ldsf ? (M.fcap > ((int64_t)1 << 14) ? 1024 : 512) : kBlock);
     if (M.rtc_block != 256 && M.rtc_block != 512 && M.rtc_block != 1024) M.rtc_block = kBlock;
     const int patbits = M.rtc_ldsf ? kFilterPatBitsLds : bs ? M.bs_pat_bits : kFilterPatBits;
-    const std::string vdefs = rtc_variant_defs(M.rtc_block, M.rtc_ldsf, patbits, bs, pf, M.bs_pf_log2, M.bs_slot_w == 96);
+    const std::string wdefs = rtc_variant_defs(M.rtc_block, M.rtc_ldsf, patbits, bs, pf, M.bs_pf_log2, M.bs_slot_w == 96);
+    // k1s for a model that does not walk (the default, walk_preferred): walk mode compiled out,
+    // so that the kernel's registers are the lockstep loop's (CVD_K1S_WALK_CODE=1: always in)
+    const bool nowalk = bs && !walk_preferred(M) && env_i("CVD_K1S_WALK_CODE", 0) == 0;
+    const std::string vdefs = wdefs + (nowalk ? kNoWalkDef : "");
     if (rtc_k1b_function(device, M.dec.m, M.bfly_x, vdefs.c_str(), &M.rtc_fn, &M.rtc_fn_multi) == 0) {
       M.rtc_bs = bs;
       M.rtc_pf = pf;
+      M.rtc_nowalk = nowalk;
+      M.rtc_walk_defs = wdefs;
       M.jit_error.clear();
       break;
     }
@@ -2391,6 +2515,9 @@ void cvd::free_model_device(cvd_model& M) {
   M.rtc_persist_grid = 0;
   M.rtc_bs = false;
   M.rtc_pf = false;
+  M.rtc_nowalk = false;
+  M.rtc_fn_walk = nullptr;
+  M.rtc_fn_multi_walk = nullptr;
   M.d_bmp = nullptr;
   M.d_bmk1 = nullptr;
   M.d_bfly = nullptr;

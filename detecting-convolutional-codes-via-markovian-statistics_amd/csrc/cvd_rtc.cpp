@@ -112,11 +112,11 @@ const char* kClangFlags[] = {"-O3", "-std=c++17", "-ffp-contract=off",
 // two entries per code: one model per launch, and several (k1b_multi, cvd_detect_multi);
 // the model's variant defines pick the butterfly kernel or its bit-sliced form (k1s)
 std::string entry_source(int m, uint64_t xm) {
-  char entry[640];
+  char entry[768];
   std::snprintf(entry, sizeof(entry),
-                "\nextern \"C\" __global__ __launch_bounds__(cvd_dev::kK1bBlock, cvd_dev::kK1bWavesPerSimd)\n"
+                "\nextern \"C\" __global__ CVD_K1B_ENTRY_ATTR __launch_bounds__(cvd_dev::kK1bBlock, cvd_dev::kK1bWavesPerSimd)\n"
                 "void cvd_k1b_spec(cvd_dev::ExpArgs a) { cvd_dev::k1b_spec_entry<%d, 0x%016llxull>(a); }\n"
-                "extern \"C\" __global__ __launch_bounds__(cvd_dev::kK1bBlock, cvd_dev::kK1bWavesPerSimd)\n"
+                "extern \"C\" __global__ CVD_K1B_ENTRY_ATTR __launch_bounds__(cvd_dev::kK1bBlock, cvd_dev::kK1bWavesPerSimd)\n"
                 "void cvd_k1b_spec_multi(cvd_dev::MultiArgs a) { cvd_dev::k1b_spec_multi_entry<%d, 0x%016llxull>(a); }\n",
                 m, (unsigned long long)xm, m, (unsigned long long)xm);
   return entry;
@@ -266,7 +266,8 @@ int cvd::rtc_k1b_function(int device, int m, uint64_t xm, const char* variant_de
     std::string t;
     while (ds >> t)
       if (t.rfind("-DCVD_K1B_BLOCK", 0) != 0 && t.rfind("-DCVD_K1B_LDSF", 0) != 0 &&
-          t.rfind("-DCVD_FILTER_PAT_BITS", 0) != 0 && t.rfind("-DCVD_K1S_PF", 0) != 0)
+          t.rfind("-DCVD_FILTER_PAT_BITS", 0) != 0 && t.rfind("-DCVD_K1S_PF", 0) != 0 &&
+          t.rfind("-DCVD_K1S_WALK=", 0) != 0)
         env_defs += " " + t;
   }
   const std::string all_defs = std::string(variant_defs ? variant_defs : "") + env_defs;

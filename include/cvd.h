@@ -344,6 +344,10 @@ int cvd_chunk_last(int64_t* out4);
  * CVD_JIT_PREBUILT=off skips it).  Only the bit-sliced codes (m = 6, k = 1, n = 2 standard
  * butterflies) have variants to build; *n_built = how many were built or found. */
 int cvd_jit_prebuild(const cvd_code* dec, const char* arch, const char* dir, int32_t* n_built);
+/* The same for the variants with walk mode compiled in, which a bit-sliced model's launch runs
+ * only when walk mode is forced on (CVD_WALK=1; the default variants leave it out, so that the
+ * lockstep kernel keeps the lockstep loop's register count). */
+int cvd_jit_prebuild_walk(const cvd_code* dec, const char* arch, const char* dir, int32_t* n_built);
 
 /* The same grid point in ONE kernel per launch, without streams in HBM: every lane
  * generates its own sequence's received words (cvd_generate's encoder and noise, bit
