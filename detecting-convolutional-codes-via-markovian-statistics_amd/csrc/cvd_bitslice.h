@@ -44,6 +44,11 @@
 
 #include "cvd_keys.h"
 
+// (removed knobs: a build that names one would silently get the code below)
+#if defined(CVD_BS_VFAST) || defined(CVD_BS_KLDS)
+#error "removed bit-slice knob: CVD_BS_VFAST and CVD_BS_KLDS no longer exist (DESIGN.md §10)"
+#endif
+
 namespace cvd {
 
 typedef unsigned int bs_u32;
@@ -119,53 +124,29 @@ CVD_HD bs_u32 bs_perm(bs_u32 hi, bs_u32 lo, bs_u32 sel) {
 // v_bitop3 / and / or / xor / add / lshrrev with VGPR, inline or literal operands issue at
 // ~2.5-2.8 cycles per wave64 instruction, the same with an SGPR (or SGPR-pair / VCC) source
 // at ~4.2, and v_lshlrev, v_or3, v_bfi, v_perm, v_cndmask at ~4.2 whatever the operands.  So
-// (CVD_BS_VFAST, default on) a bitop3 mask constant is moved into a VGPR once per use site
-// group (VOP3 takes no literal here; the compiler's own choice is an SGPR), x << 1 is an add,
-// and the step's mu mask is a VGPR value (the compiler's form: v_cndmask on VCC).
-// (bits, for A/Bs: 1 the masks, 2 the add, 4 the mu mask, 8 the zero test's OR as a bitop3)
-#ifndef CVD_BS_VFAST
-#define CVD_BS_VFAST 15
-#endif
-// CVD_BS_KLDS (timing A/B, default 0): the six flip / canonicalisation masks come from a
-// block-shared table (filled with the kernel's other LDS tables) instead of a v_mov per use
-// group: an LDS read the compiler may keep in a VGPR across the step loop
-#ifndef CVD_BS_KLDS
-#define CVD_BS_KLDS 0
-#endif
-constexpr int bs_kmask_index(bs_u32 C) {
-  return C == 0xAAAAAAAAu ? 0 : C == 0xCCCCCCCCu ? 1 : C == 0xF0F0F0F0u ? 2
-       : C == 0x55555555u ? 3 : C == 0x33333333u ? 4 : C == 0x0F0F0F0Fu ? 5 : -1;
-}
-constexpr bs_u32 kBsKmasks[6] = {0xAAAAAAAAu, 0xCCCCCCCCu, 0xF0F0F0F0u, 0x55555555u, 0x33333333u, 0x0F0F0F0Fu};
-#if defined(__HIPCC__) || defined(__HIPCC_RTC__) || defined(__HIP_DEVICE_COMPILE__)
-__device__ __forceinline__ bs_u32* bs_kmask_lds() {
-  __shared__ bs_u32 s_km[8];
-  return s_km;
-}
-#endif
+// on the device a bitop3 mask constant is moved into a VGPR once per use site group (VOP3 takes
+// no literal here; the compiler's own choice is an SGPR), x << 1 is an add, the step's mu mask is
+// a VGPR value (the compiler's form: v_cndmask on VCC) and the zero test's OR a bitop3.
 template <bs_u32 C>
 CVD_HD bs_u32 bs_vconst() {
 #if defined(__HIP_DEVICE_COMPILE__)
-  if constexpr (CVD_BS_KLDS != 0 && bs_kmask_index(C) >= 0) {
-    return bs_kmask_lds()[bs_kmask_index(C)];
-  } else if constexpr ((CVD_BS_VFAST & 1) != 0) {
-    bs_u32 c;
-    asm volatile("v_mov_b32 %0, %1" : "=v"(c) : "i"(C));
-    return c;
-  }
-#endif
+  bs_u32 c;
+  asm volatile("v_mov_b32 %0, %1" : "=v"(c) : "i"(C));
+  return c;
+#else
   return C;
+#endif
 }
 CVD_HD bs_u32 bs_vreg(bs_u32 x) {   // an opaque VGPR copy (no SGPR / VCC-select forms of its uses)
 #if defined(__HIP_DEVICE_COMPILE__)
-  if constexpr ((CVD_BS_VFAST & 4) != 0) asm volatile("" : "+v"(x));
+  asm volatile("" : "+v"(x));
 #endif
   return x;
 }
 template <int S>
 CVD_HD bs_u32 bs_shl(bs_u32 x) {
 #if defined(__HIP_DEVICE_COMPILE__)
-  if constexpr ((CVD_BS_VFAST & 2) != 0 && S == 1) {
+  if constexpr (S == 1) {
     bs_u32 r;
     asm("v_add_u32_e32 %0, %1, %1" : "=v"(r) : "v"(x));
     return r;
@@ -455,7 +436,7 @@ CVD_HD void bs_step_core(const bs_u32 (&R)[2][4], const bs_u32 (&e0)[2], const b
   // mu first: a zero state with e even
   bs_u32 z[2];
   for (int r = 0; r < 2; ++r) {
-    const bs_u32 t = (CVD_BS_VFAST & 8) ? bs_bop3<kTtOr3>(R[r][0], R[r][1], R[r][2]) : R[r][0] | R[r][1] | R[r][2];
+    const bs_u32 t = bs_bop3<kTtOr3>(R[r][0], R[r][1], R[r][2]);
     z[r] = bs_bop3<kTtNor3>(t, R[r][3], e0[r]);
   }
   const bool zero_hit = (z[0] | z[1]) != 0u;
@@ -486,7 +467,7 @@ CVD_HD void bs_step_core(const bs_u32 (&R)[2][4], const bs_u32 (&e0)[2], const b
   if (all1) *all1 = one;
 }
 
-// The same step with mu's branch-metric planes from a table (CVD_BS_ETAB2): for each (phase,
+// The same step with mu's branch-metric planes from a table (the kernel's form): for each (phase,
 // y) the planes the adds take once mu is known -- the own and partner addends' bit 0 with mu
 // folded in (e0 ^ M), bit 1 and bits 2-3 -- are precomputed for mu = 0 and mu = 1, so the step
 // reads them (the kernel: from LDS at a mu-dependent offset) instead of selecting them with M:
@@ -523,7 +504,7 @@ CVD_HD void bs_step_core_tab(const bs_u32 (&R)[2][4], const bs_u32 (&e0)[2], Loa
   constexpr int L5 = bs_sigma(PH, 5);
   bs_u32 z[2];
   for (int r = 0; r < 2; ++r) {
-    const bs_u32 t = (CVD_BS_VFAST & 8) ? bs_bop3<kTtOr3>(R[r][0], R[r][1], R[r][2]) : R[r][0] | R[r][1] | R[r][2];
+    const bs_u32 t = bs_bop3<kTtOr3>(R[r][0], R[r][1], R[r][2]);
     z[r] = bs_bop3<kTtNor3>(t, R[r][3], e0[r]);
   }
   const bool zero_hit = (z[0] | z[1]) != 0u;

@@ -622,10 +622,8 @@ void build_hash(cvd_model& Mo) {
   while (bcap < ((int64_t)1 << bload) * Mo.n_rows) bcap <<= 1;
   // the kernel addresses the directory, the two-step records and the images by 32-bit byte
   // offsets: past 4 GiB (over ~2·10^6 rows) the model keeps the nibble tables
-  // directory slots of 256 B, or three 128-B lines {two phase images, record} (CVD_BS_SLOT3=1)
-  const char* s3 = std::getenv("CVD_BS_SLOT3");
-  Mo.bs_slot_w = s3 && s3[0] == '1' ? 96 : 64;
-  if (bcap * 4 * Mo.bs_slot_w > ((int64_t)1 << 32) || Mo.n_rows * 512 > ((int64_t)1 << 32)) Mo.bs = false;
+  constexpr int kSlotW = 64;   // dwords per directory slot (256 B)
+  if (bcap * 4 * kSlotW > ((int64_t)1 << 32) || Mo.n_rows * 512 > ((int64_t)1 << 32)) Mo.bs = false;
   Mo.h_bfilt.clear(); Mo.h_bfilt_lds.clear(); Mo.h_bkey_rows.clear(); Mo.h_bkey_slot.clear(); Mo.h_bdkey.clear();
   Mo.h_bpf.clear();
   Mo.bhcap = 0; Mo.bmax_probe = 0;
@@ -645,7 +643,6 @@ void build_hash(cvd_model& Mo) {
     const unsigned bnpat = 1u << Mo.bs_pat_bits;
     Mo.bhcap = bcap;
     constexpr int kRecW = 48, kImgW = 48;
-    const int kSlotW = Mo.bs_slot_w;
     Mo.h_bkey_rows.assign((size_t)Mo.n_rows * kSlotW, 0u);   // (the empty slots: zero, c = 0 in every record)
     Mo.h_bkey_slot.assign((size_t)Mo.n_rows, 0u);
     Mo.h_bfilt.assign((size_t)fcap, 0u);
@@ -687,13 +684,9 @@ void build_hash(cvd_model& Mo) {
       const uint32_t* rec = Mo.h_drow.data() + (size_t)dev_of[(size_t)i] * Mo.h_rsw;
       for (int ph = 0; ph < 6; ++ph) {
         bs_image(Mo.keys.data() + (size_t)i * M, ph, dk + 8 * ph);
-        // (slot3: image of phase ph at dword 32 (ph / 2) + 8 (ph % 2) of the line ph / 2)
-        std::memcpy(sp + (kSlotW == 96 ? 32 * (ph / 2) + 8 * (ph % 2) : 8 * ph), dk + 8 * ph, 8 * sizeof(uint32_t));
+        std::memcpy(sp + 8 * ph, dk + 8 * ph, 8 * sizeof(uint32_t));
       }
-      if (kSlotW == 96)
-        for (int k = 0; k < 3; ++k) std::memcpy(sp + 32 * k + 16, rec, sizeof(uint32_t) * 16);
-      else
-        std::memcpy(sp + kRecW, rec, sizeof(uint32_t) * 16);
+      std::memcpy(sp + kRecW, rec, sizeof(uint32_t) * 16);
     });
   }
   pt.mark("  bit-sliced tables: images + records");
@@ -703,10 +696,7 @@ void build_hash(cvd_model& Mo) {
   Mo.h_t2.clear();
   Mo.h_t2c.clear();
   Mo.h_vtab.clear();
-  // (CVD_BS_T2=1: for the bit-sliced lockstep lanes too, whose kernel reads them with
-  // -DCVD_K1S_T2=1 in CVD_JIT_DEFINES; timing studies, cvd_k1s.h)
-  const char* bt2 = std::getenv("CVD_BS_T2");
-  if (Mo.dec.k == 1 && R == 4 && (walk_preferred(Mo) || (Mo.bs && bt2 && bt2[0] == '1'))) {
+  if (Mo.dec.k == 1 && R == 4 && walk_preferred(Mo)) {
     Mo.h_t2.assign((size_t)Mo.n_rows * 16 * 8, 0u);
     parallel_for(Mo.n_rows, [&](int64_t d, int) {
       const uint32_t* a0 = Mo.h_drow.data() + (size_t)d * Mo.h_rsw;

@@ -2380,12 +2380,11 @@ static int ck_finish(std::vector<CkGroup>& gs, hipStream_t st) {
   return rc;
 }
 
-std::string cvd::rtc_variant_defs(int block, bool ldsf, int patbits, bool bs, bool pf, int pf_log2, bool slot3) {
+std::string cvd::rtc_variant_defs(int block, bool ldsf, int patbits, bool bs, bool pf, int pf_log2) {
   return "-DCVD_K1B_BLOCK=" + std::to_string(block) + (ldsf ? " -DCVD_K1B_LDSF=1" : "") +
          (patbits != kFilterPatBits ? " -DCVD_FILTER_PAT_BITS=" + std::to_string(patbits) : "") +
          (bs ? " -DCVD_K1B_BITSLICE=1" : "") + (pf ? " -DCVD_K1S_PF=1" : "") +
-         (pf && pf_log2 != kBsPfLog2Bits ? " -DCVD_K1S_PF_LOG2=" + std::to_string(pf_log2) : "") +
-         (bs && slot3 ? " -DCVD_K1S_SLOT3=1" : "");
+         (pf && pf_log2 != kBsPfLog2Bits ? " -DCVD_K1S_PF_LOG2=" + std::to_string(pf_log2) : "");
 }
 
 int cvd::upload_model(cvd_model& M, int device) {
@@ -2417,7 +2416,7 @@ int cvd::upload_model(cvd_model& M, int device) {
     if ((rc = dev_copy(M.d_vtab, M.h_vtab))) return rc;
     if ((rc = dev_copy(M.d_bfilt, M.h_bfilt))) return rc;
     if ((rc = dev_copy(M.d_bfilt_lds, M.h_bfilt_lds))) return rc;
-    if ((rc = dev_directory(M.d_bkey, M.h_bkey_rows, M.h_bkey_slot, M.bhcap, M.bs_slot_w, 0u))) return rc;
+    if ((rc = dev_directory(M.d_bkey, M.h_bkey_rows, M.h_bkey_slot, M.bhcap, 1 << cvd_dev::kBsSlotShift, 0u))) return rc;
     if ((rc = dev_copy(M.d_bdkey, M.h_bdkey))) return rc;
     if ((rc = dev_copy(M.d_bpf, M.h_bpf))) return rc;
     if ((rc = dev_copy(M.d_bmp, M.bmp))) return rc;
@@ -2454,7 +2453,7 @@ int cvd::upload_model(cvd_model& M, int device) {
     M.rtc_block = pf ? (M.bs_pf_log2 >= 20 ? 1024 : 512) : env_i("CVD_K1B_BLOCK", M.rtc_ldsf ? (M.fcap > ((int64_t)1 << 14) ? 1024 : 512) : kBlock);
     if (M.rtc_block != 256 && M.rtc_block != 512 && M.rtc_block != 1024) M.rtc_block = kBlock;
     const int patbits = M.rtc_ldsf ? kFilterPatBitsLds : bs ? M.bs_pat_bits : kFilterPatBits;
-    const std::string wdefs = rtc_variant_defs(M.rtc_block, M.rtc_ldsf, patbits, bs, pf, M.bs_pf_log2, M.bs_slot_w == 96);
+    const std::string wdefs = rtc_variant_defs(M.rtc_block, M.rtc_ldsf, patbits, bs, pf, M.bs_pf_log2);
     // k1s for a model that does not walk (the default, walk_preferred): walk mode compiled out,
     // so that the kernel's registers are the lockstep loop's (CVD_K1S_WALK_CODE=1: always in)
     const bool nowalk = bs && !walk_preferred(M) && env_i("CVD_K1S_WALK_CODE", 0) == 0;

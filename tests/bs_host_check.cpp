@@ -6,7 +6,7 @@
 // r' with step(D, r') == D_t (the T_ref count, Pd_plotter.py:89-99); the digest hash of
 // the new planes equals the host key of D_t (bs_digest + bs_key_hash), and bs_canon<f> maps
 // every phase-f digest image to the phase-0 one; the table form of the step (bs_step_core_tab,
-// CVD_BS_ETAB2) equals the plain one.  TEST INFRASTRUCTURE ONLY.
+// the kernel's) equals the plain one.  TEST INFRASTRUCTURE ONLY.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -64,7 +64,7 @@ static void run_step(const bs_u32 (&R)[2][4], const BsE& E, bs_u32 (&N)[2][4], b
                      bs_u32& hpl) {
   bs_step_core<PH, kUni>(R, E.e0, E.e1, E.ez, N, mu, c);
   bs_digest_hash<(PH + 1) % 6>(N, hph, hpl);
-  // the table form (CVD_BS_ETAB2) must give the same planes, mu and count
+  // the table form (the kernel's) must give the same planes, mu and count
   bs_u32 N2[2][4], mu2, c2;
   bs_step_core_tab<PH, kUni>(R, E.e0, [&](bool zero_hit) { return bs_mu_planes(E, !zero_hit); }, N2, mu2, c2);
   bool same = mu2 == mu && c2 == c;
