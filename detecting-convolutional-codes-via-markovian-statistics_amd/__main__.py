@@ -36,7 +36,7 @@
   ... decode --code C --input FILE [--format bytes|lsb|msb|soft] [--nbits B] [--start S] [--T T]
              [--out-bits FILE.npy] [--puncture SPEC [--sync T0]]
              [--frame T [--frame-count F] [--frame-stride B | --frame-offsets FILE.npy]
-              [--start-state S|any] [--end-state S|any]]
+              [--start-state S|any] [--end-state S|any] | [--tail-biting [--laps I]]]
       (nothing in the reference) -- what was sent: the hard-decision Viterbi decoder of the
       k = 1 code C over the capture from bit S (cvd_viterbi_decode: the Eq. 4-5 recursion with
       its survivor decisions kept, exact whatever the block split); writes the decoded bits to
@@ -68,6 +68,14 @@
       w = ceil(T/32): a row per frame, LSB-first) and <save-dir>/decode_frames.csv, a row per
       frame: frame, offset, status (0 decoded, 1 skipped), distance, errors, counted,
       start_state, end_state; prints the totals and p = errors / counted.
+      --frame T --tail-biting: the frames are tail-biting (LTE PBCH / PDCCH, 802.16 FCH: the
+      encoder starts in the state of the frame's own last m bits and no tail bits are sent),
+      decoded by the wrap-around Viterbi algorithm (cvd_viterbi_decode_frames_tailbiting and its
+      punctured and soft siblings) with at most --laps I laps (1..8, default 4).  An error
+      together with --start-state / --end-state (neither state is known), --T or --sync.  The
+      CSV gains the column laps and status reads 0 tail-biting best path, 1 skipped, 2 best
+      tail-biting survivor of the last lap, 3 no tail-biting survivor (start_state !=
+      end_state); the summary adds the numbers of such frames and the mean laps.
 
 Codes: the BASELINE configurations (m2, m6, r23_m4), the demo presets (example:1,
 example:2, demo_script.py:35-52), or oct:G0,G1[,G2] -- k = 1 generators in octal (MSB =
@@ -85,6 +93,7 @@ import sys
 
 from . import (CONFIG_CODES, DEFAULTS, EXAMPLE_CODES, compute_error_exponent, default_template,
                decode_capture, decode_capture_punctured, decode_capture_soft, decode_frames, decode_frames_soft,
+               decode_frames_tailbiting, decode_frames_tailbiting_soft,
                find_parity_checks,
                learn_transition_tensor, octal_to_taps, parity_experiment, parity_vector_to_equation, parity_vectors,
                puncture_pattern, punctured_bits, run_experiment, scan_capture, sync_punctured, sync_punctured_soft)
@@ -222,16 +231,30 @@ def parser():
                    help="capture bits (soft: values) from one frame's start to the next (default: a frame's own)")
     d.add_argument("--frame-offsets", default=None, metavar="FILE.npy",
                    help=".npy of int64: where each frame begins (instead of --start and --frame-stride)")
-    d.add_argument("--start-state", type=frame_state, default=0, metavar="S|any",
+    d.add_argument("--start-state", type=frame_state, default=0, metavar="S|any", action=BoundaryState,
                    help="with --frame: the encoder's state before a frame, or any (default 0)")
-    d.add_argument("--end-state", type=frame_state, default=0, metavar="S|any",
+    d.add_argument("--end-state", type=frame_state, default=0, metavar="S|any", action=BoundaryState,
                    help="with --frame: the encoder's state after a frame, or any (default 0: m zero tail bits)")
+    d.add_argument("--tail-biting", action="store_true",
+                   help="with --frame: the frames are tail-biting, decoded by the wrap-around Viterbi algorithm "
+                        "(not with --start-state or --end-state)")
+    d.add_argument("--laps", type=int, default=None, metavar="I",
+                   help="with --tail-biting: at most I laps over a frame (1..8, default 4)")
+    d.set_defaults(states_given=False)
 
     c = sub.add_parser("compare", help="P_err figures of both detectors (plots_compare.py)")
     c.add_argument("--hybrid", required=True, help="CSV of the experiment subcommand")
     c.add_argument("--baseline", required=True, help="CSV of the parity subcommand")
     c.add_argument("--outdir", default="plots")
     return ap
+
+
+class BoundaryState(argparse.Action):
+    """--start-state / --end-state: the value, and that one of them was given."""
+
+    def __call__(self, parser, namespace, values, option_string=None):
+        setattr(namespace, self.dest, values)
+        namespace.states_given = True
 
 
 def frame_state(text):
@@ -256,6 +279,8 @@ def parse_args(argv=None):
             if (a.frame_count is not None or a.frame_stride is not None or a.frame_offsets is not None
                     or a.start_state != 0 or a.end_state != 0):
                 ap.error("decode: --frame-count, --frame-stride, --frame-offsets, --start-state and --end-state need --frame")
+            if a.tail_biting:
+                ap.error("decode: --tail-biting needs --frame")
         else:
             if a.T is not None or a.sync is not None:
                 ap.error("decode: --frame decodes frames of T steps each; it does not go with --T or --sync")
@@ -263,6 +288,10 @@ def parse_args(argv=None):
                 ap.error("decode: --frame-offsets and --frame-stride exclude one another")
             if a.format == "soft" and a.puncture is not None:
                 ap.error("decode: --frame with --format soft does not take --puncture")
+            if a.tail_biting and a.states_given:
+                ap.error("decode: --tail-biting does not go with --start-state or --end-state: neither state is known")
+        if a.laps is not None and not a.tail_biting:
+            ap.error("decode: --laps needs --tail-biting")
     return a
 
 
@@ -402,6 +431,7 @@ def cmd_identify(a):
 
 DECODE_COLUMNS = ["T", "errors", "ber", "start_state", "end_state", "blocks", "forward_reruns", "trace_fixups"]
 FRAME_COLUMNS = ["frame", "offset", "status", "distance", "errors", "counted", "start_state", "end_state"]
+TAILBITING_COLUMNS = FRAME_COLUMNS + ["laps"]
 
 
 def cmd_decode_frames(a, n, m, g1):
@@ -413,14 +443,18 @@ def cmd_decode_frames(a, n, m, g1):
         if offsets.dtype != np.int64:
             raise SystemExit(f"{a.frame_offsets}: frame offsets are int64, not {offsets.dtype}")
         offsets = offsets.reshape(-1)
-    kw = dict(F=a.frame_count, start=a.start, stride=a.frame_stride, offsets=offsets, start_state=a.start_state,
-              end_state=a.end_state)
+    kw = dict(F=a.frame_count, start=a.start, stride=a.frame_stride, offsets=offsets)
+    if a.tail_biting:
+        kw["max_laps"] = a.laps
+        hard, soft = decode_frames_tailbiting, decode_frames_tailbiting_soft
+    else:
+        kw.update(start_state=a.start_state, end_state=a.end_state)
+        hard, soft = decode_frames, decode_frames_soft
     try:
         if a.format == "soft":
-            res = decode_frames_soft(n, m, g1, load_soft_capture(a.input, a.nbits), a.frame, **kw)
+            res = soft(n, m, g1, load_soft_capture(a.input, a.nbits), a.frame, **kw)
         else:
-            res = decode_frames(n, m, g1, load_capture(a.input), a.frame, keep=a.puncture, format=a.format,
-                                nbits=a.nbits, **kw)
+            res = hard(n, m, g1, load_capture(a.input), a.frame, keep=a.puncture, format=a.format, nbits=a.nbits, **kw)
     except ValueError as e:
         raise SystemExit(f"decode: {e}")
     frames = res["frames"].cpu().numpy()
@@ -436,12 +470,16 @@ def cmd_decode_frames(a, n, m, g1):
         np.save(f, res["bits"].cpu().numpy())
     with open(out, "w", newline="") as f:
         wr = csv.writer(f)
-        wr.writerow(FRAME_COLUMNS)
+        wr.writerow(TAILBITING_COLUMNS if a.tail_biting else FRAME_COLUMNS)
         for i, r in enumerate(frames.tolist()):
-            wr.writerow([i, int(offsets[i]), r[3], r[0], r[4], r[5], r[1], r[2]])
+            wr.writerow([i, int(offsets[i]), r[3], r[0], r[4], r[5], r[1], r[2]] + ([r[6]] if a.tail_biting else []))
     print(f"Decoded {res['decoded']} frames of {res['T']} steps ({res['skipped']} skipped): distance "
           f"{res['total_distance']}, {res['total_errors']} channel errors in {res['total_counted']} positions, "
           f"p = {res['ber']!r}")
+    if a.tail_biting:
+        print(f"Tail-biting: {res['fallback']} frames fell back to the last lap's best tail-biting survivor, "
+              f"{res['open']} have none (start_state != end_state); "
+              f"{res['total_laps'] / max(res['decoded'], 1):.3f} laps per frame")
     print("Saved bits to", out_bits, f"({res['F']} rows of {res['bits'].shape[1]} bytes)")
     print("Saved results to", out)
     return 0

@@ -172,6 +172,25 @@ EXPORTS = {
                                                       ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
                                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                       ctypes.c_void_p]),
+    "cvd_viterbi_tailbiting_workspace_bytes": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                                                ctypes.c_int64, ctypes.c_int32]),
+    "cvd_viterbi_decode_frames_tailbiting": (ctypes.c_int, [ctypes.POINTER(cvd_code), ctypes.c_void_p, ctypes.c_int64,
+                                                            ctypes.c_int32, ctypes.c_int64, ctypes.c_int64,
+                                                            ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32,
+                                                            ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
+                                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "cvd_viterbi_decode_frames_tailbiting_punctured": (ctypes.c_int, [ctypes.POINTER(cvd_code), ctypes.c_char_p,
+                                                                      ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64,
+                                                                      ctypes.c_int32, ctypes.c_int64, ctypes.c_int64,
+                                                                      ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32,
+                                                                      ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
+                                                                      ctypes.c_void_p, ctypes.c_void_p,
+                                                                      ctypes.c_void_p]),
+    "cvd_viterbi_decode_frames_tailbiting_soft": (ctypes.c_int, [ctypes.POINTER(cvd_code), ctypes.c_void_p,
+                                                                 ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                                                                 ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32,
+                                                                 ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
+                                                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "cvd_count_transitions": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
                                              ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
     "cvd_chernoff_build": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,

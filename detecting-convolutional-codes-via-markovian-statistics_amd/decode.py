@@ -378,18 +378,9 @@ def _frame_state(name, s, m):
     return s
 
 
-def _frames(who, entry, lead, fmt, cap, nbits, n, m, T, span, F, start, stride, offsets, start_state, end_state, soft,
-            dev):
-    """One call of the library's frame decoder `entry`(*lead, capture, nbits, *fmt, start, stride,
-    offsets, F, T, start_state, end_state, bits, frames, stats, work, stream): decode_frames' dict.
-    span: the capture bits (values) of a frame."""
-    T = int(T)
-    if not 1 <= T <= FRAME_MAX_T:
-        raise ValueError(f"T = {T}: a frame has 1..{FRAME_MAX_T} steps")
-    ss, es = _frame_state("start_state", start_state, m), _frame_state("end_state", end_state, m)
-    if ss >= 0 and es >= 0 and T < m:
-        raise ValueError(f"T = {T} < m = {m}: with both states fixed the end state is not reachable")
-    w = (T + 31) // 32
+def _frame_placement(nbits, span, w, F, start, stride, offsets, dev):
+    """Where the frames of `span` capture positions lie: (offsets on the device or None, F, start,
+    stride) as the library's frame calls take them."""
     off = None
     if offsets is not None:
         off = torch.from_numpy(np.ascontiguousarray(offsets)) if isinstance(offsets, np.ndarray) else offsets
@@ -410,6 +401,22 @@ def _frames(who, entry, lead, fmt, cap, nbits, n, m, T, span, F, start, stride, 
             raise ValueError(f"F = {F}: {fit} frames of {span} capture positions fit from {start} at stride {stride}")
     if F * w >= 1 << 31:
         raise ValueError(f"F = {F} frames of {w} words: the decoded bits must stay below 2^31 words")
+    return off, F, start, stride
+
+
+def _frames(who, entry, lead, fmt, cap, nbits, n, m, T, span, F, start, stride, offsets, start_state, end_state, soft,
+            dev):
+    """One call of the library's frame decoder `entry`(*lead, capture, nbits, *fmt, start, stride,
+    offsets, F, T, start_state, end_state, bits, frames, stats, work, stream): decode_frames' dict.
+    span: the capture bits (values) of a frame."""
+    T = int(T)
+    if not 1 <= T <= FRAME_MAX_T:
+        raise ValueError(f"T = {T}: a frame has 1..{FRAME_MAX_T} steps")
+    ss, es = _frame_state("start_state", start_state, m), _frame_state("end_state", end_state, m)
+    if ss >= 0 and es >= 0 and T < m:
+        raise ValueError(f"T = {T} < m = {m}: with both states fixed the end state is not reachable")
+    w = (T + 31) // 32
+    off, F, start, stride = _frame_placement(nbits, span, w, F, start, stride, offsets, dev)
     L = _lib.lib()
     call = getattr(L, entry)
     wbytes = int(L.cvd_viterbi_frames_workspace_bytes(n, m, T, F, int(soft)))
@@ -482,3 +489,90 @@ def decode_frames_soft(n, m, gen, soft, T, F=None, start=0, stride=None, offsets
     cap, nvals = _soft_buffer(soft, dev)
     return _frames("decode_frames_soft", "cvd_viterbi_decode_frames_soft", (code.c,), (), cap, nvals, n, m, T, n * T, F,
                    start, stride, offsets, start_state, end_state, True, dev)
+
+
+# ──────────────────────────── tail-biting frames ────────────────────────────
+
+TAILBITING_LAPS = 4      # include/cvd.h CVD_VITERBI_TAILBITING_LAPS
+TAILBITING_MAX_LAPS = 8  # include/cvd.h CVD_VITERBI_TAILBITING_MAX_LAPS
+
+
+def _tailbiting(who, entry, lead, fmt, cap, nbits, n, m, T, span, F, start, stride, offsets, max_laps, soft, dev):
+    """One call of the library's tail-biting decoder `entry`(*lead, capture, nbits, *fmt, start,
+    stride, offsets, F, T, max_laps, bits, frames, stats, work, stream): decode_frames_tailbiting's
+    dict.  span: the capture bits (values) of a frame."""
+    T = int(T)
+    if not 1 <= T <= FRAME_MAX_T:
+        raise ValueError(f"T = {T}: a frame has 1..{FRAME_MAX_T} steps")
+    laps = 0 if max_laps is None else int(max_laps)
+    if max_laps is not None and not 1 <= laps <= TAILBITING_MAX_LAPS:
+        raise ValueError(f"max_laps = {max_laps}: 1..{TAILBITING_MAX_LAPS} laps, or None for {TAILBITING_LAPS}")
+    w = (T + 31) // 32
+    off, F, start, stride = _frame_placement(nbits, span, w, F, start, stride, offsets, dev)
+    L = _lib.lib()
+    call = getattr(L, entry)
+    wbytes = int(L.cvd_viterbi_tailbiting_workspace_bytes(n, m, T, F, int(soft)))
+    if wbytes < 0:
+        # the decoder itself names an unsupported code shape
+        _lib.check(call(*lead, None, 0, *fmt, 0, 1, None, 0, T, laps, None, None, None, None, None))
+        _lib.check(wbytes)
+    with torch.cuda.device(dev):
+        bits = torch.empty((F, 4 * w), dtype=torch.uint8, device=dev)
+        frames = torch.empty((F, 8), dtype=torch.int32, device=dev)
+        s = [0, 0, 0, 0, 0, w, 0, 0, 0]
+        if F:
+            free = torch.cuda.mem_get_info(dev)[0]
+            if wbytes > free:
+                raise MemoryError(f"{who}: the workspace of {F} frames of T = {T} steps (m = {m}) is {wbytes} bytes, "
+                                  f"{free} bytes of device memory are free: decode the frames in pieces")
+            stats = torch.zeros(9, dtype=torch.int64, device=dev)
+            work = torch.empty(wbytes, dtype=torch.uint8, device=dev) if wbytes else None
+            _lib.check(call(*lead, ctypes.c_void_p(cap.data_ptr()), nbits, *fmt, start, stride,
+                            ctypes.c_void_p(off.data_ptr()) if off is not None else None, F, T, laps,
+                            ctypes.c_void_p(bits.data_ptr()), ctypes.c_void_p(frames.data_ptr()),
+                            ctypes.c_void_p(stats.data_ptr()),
+                            ctypes.c_void_p(work.data_ptr()) if work is not None else None, _stream_ptr()))
+            s = stats.cpu().tolist()     # synchronises: cap, off and work may be freed on return
+    return {"bits": bits, "frames": frames, "distance": frames[:, 0], "start_states": frames[:, 1],
+            "end_states": frames[:, 2], "status": frames[:, 3], "errors": frames[:, 4], "counted": frames[:, 5],
+            "laps": frames[:, 6], "T": T, "F": F, "decoded": int(s[1]), "skipped": int(s[2]),
+            "total_distance": int(s[0]), "total_errors": int(s[3]), "total_counted": int(s[4]), "words": int(s[5]),
+            "fallback": int(s[6]), "open": int(s[7]), "total_laps": int(s[8]), "ber": s[3] / s[4] if s[4] else 0.0}
+
+
+def decode_frames_tailbiting(n, m, gen, capture, T, F=None, start=0, stride=None, offsets=None, max_laps=None,
+                             keep=None, format="bytes", nbits=None, device=None):
+    """cvd_viterbi_decode_frames_tailbiting: F tail-biting frames of T steps each of the k = 1 code
+    gen[j][i][d] (LTE PBCH / PDCCH, 802.16 FCH: the encoder starts in the state of the frame's own
+    last m bits, so s_0 = s_T and neither is known), decoded in one call by the wrap-around Viterbi
+    algorithm of include/cvd.h with at most max_laps laps (1..8; None: the library's default, 4).
+    The frames are placed as decode_frames places them (start, stride, F, or offsets); keep: the
+    frames are punctured (cvd_viterbi_decode_frames_tailbiting_punctured).
+    Returns decode_frames' dict with frames a device int32 [F, 8] and its further column view laps;
+    status is 0 (the best path is tail-biting), 2 (the best tail-biting survivor of the last lap),
+    3 (no tail-biting survivor: s_0 != s_T) or 1 (skipped); the further totals fallback (frames of
+    status 2), open (status 3) and total_laps; ber = total_errors / total_counted."""
+    dev = device if isinstance(device, torch.device) else _require_gpu(device)
+    n, m, T = int(n), int(m), int(T)
+    code = as_code(gen, m, 1, n)
+    cap, fmt, nbits = capture_buffer(capture, format, nbits, dev)
+    if keep is None:
+        return _tailbiting("decode_frames_tailbiting", "cvd_viterbi_decode_frames_tailbiting", (code.c,), (fmt,), cap,
+                           nbits, n, m, T, n * T, F, start, stride, offsets, max_laps, False, dev)
+    keep = puncture_pattern(keep, n)
+    return _tailbiting("decode_frames_tailbiting", "cvd_viterbi_decode_frames_tailbiting_punctured",
+                       (code.c, bytes(keep), len(keep)), (fmt,), cap, nbits, n, m, T, punctured_bits(max(T, 0), keep), F,
+                       start, stride, offsets, max_laps, False, dev)
+
+
+def decode_frames_tailbiting_soft(n, m, gen, soft, T, F=None, start=0, stride=None, offsets=None, max_laps=None,
+                                  device=None):
+    """cvd_viterbi_decode_frames_tailbiting_soft: decode_frames_tailbiting over a soft capture (int8,
+    as decode_capture_soft takes it); start, stride and offsets count values.  distance is the soft
+    distance of a frame's path, errors its sign disagreements, counted its non-erased values."""
+    dev = device if isinstance(device, torch.device) else _require_gpu(device)
+    n, m, T = int(n), int(m), int(T)
+    code = as_code(gen, m, 1, n)
+    cap, nvals = _soft_buffer(soft, dev)
+    return _tailbiting("decode_frames_tailbiting_soft", "cvd_viterbi_decode_frames_tailbiting_soft", (code.c,), (), cap,
+                       nvals, n, m, T, n * T, F, start, stride, offsets, max_laps, True, dev)

@@ -603,7 +603,7 @@ int cvd_soft_depuncture(const int8_t* d_in, int64_t nvals, int64_t start,
                         int8_t* d_out, void* stream);
 
 /* ---- framed captures: a batch of terminated frames in one call (nothing in the reference) ----
- * 802.11a/g PPDUs, GSM bursts, CCSDS / AX.25-style packets and LTE control blocks are frames: a
+ * 802.11a/g PPDUs, GSM bursts and CCSDS / AX.25-style packets are terminated frames: a
  * frame starts in a known state (0) and is driven back to a known state by m tail bits, and a
  * capture holds thousands to millions of them, at a regular stride or at offsets that a
  * sync-word search found.  These calls decode F frames of T steps each in one launch, with the
@@ -677,6 +677,89 @@ int cvd_viterbi_decode_frames_soft(const cvd_code* code, const int8_t* d_soft, i
                                    int64_t start, int64_t stride, const int64_t* d_offsets, int64_t F, int32_t T,
                                    int32_t start_state, int32_t end_state,
                                    uint32_t* d_bits, int32_t* d_frames, int64_t* d_stats, void* d_work, void* stream);
+
+/* ---- tail-biting frames: wrap-around Viterbi, batched in one call (nothing in the reference) ----
+ * LTE control blocks (PBCH, PDCCH / DCI: (133,171,165), 24 to about 100 steps), 802.16 FCH and
+ * bursts ((171,133), punctured) and the IS-54 / EDGE control channels are tail-biting frames: the
+ * encoder starts in the state that the frame's own last m information bits leave it in, so it
+ * ends in the state it started in and no tail bits are sent.  Neither boundary state is known
+ * to the decoder; what is known is that they are equal.
+ * Inherited unchanged from the cvd_viterbi_decode_frames* contract above: the code shapes, the
+ * capture formats with their alignment and readability rule, the placement of the frames
+ * (stride mode, or d_offsets with skipped frames), 1 <= T <= CVD_VITERBI_FRAME_MAX_T, the metric
+ * of each flavour (in the punctured call step t is in column t mod period in every lap), states,
+ * branches and the tie rule, the layout of d_bits, F*w < 2^31, and F == 0.  There are no
+ * start_state / end_state arguments.
+ * max_laps = I, 1 <= I <= CVD_VITERBI_TAILBITING_MAX_LAPS; 0: CVD_VITERBI_TAILBITING_LAPS. */
+#define CVD_VITERBI_TAILBITING_LAPS 4
+#define CVD_VITERBI_TAILBITING_MAX_LAPS 8
+/* The decoder of one frame (the wrap-around Viterbi algorithm; a sequential decoder written from
+ * this text reproduces the result bit for bit).  E^0(s) = 0 for all s.  Laps l = 1, 2, ...:
+ *   forward    T steps of the inherited recursion from D^l_0 = E^{l-1}, unnormalised within the
+ *              lap, decisions dec^l_t(s') recorded; every lap reads the same T received words.
+ *   normalise  E^l(s) = D^l_T(s) - min_s D^l_T(s).
+ *   trace      for every end state e, a^l(e) = the state at step 0 that the inherited traceback
+ *              reaches from s_T = e through dec^l.
+ *   B^l = {e : a^l(e) = e}, the tail-biting survivors; c^l(e) = D^l_T(e) - D^l_0(a^l(e)), the
+ *   cost of e's survivor over the frame's own T steps; e* = the lowest-index state of minimal
+ *   D^l_T.
+ *   e* in B^l: stop, return the survivor of e* with status 0.
+ *   Otherwise lap l is the last if l = I, or if l >= 2 and E^l = E^{l-1} as vectors (every
+ *   further lap would repeat this one exactly).  On the last lap: B^l not empty: return the
+ *   survivor of the e in B^l of minimal c^l(e), lowest index on ties, with status 2; B^l empty:
+ *   return the survivor of e*, which is not tail-biting (s_0 != s_T), with status 3.
+ *   Not the last lap: go on to lap l + 1.
+ * The returned path gives u_t, s_0 = a^l(e) and s_T = e as the inherited traceback does.  T < m
+ * is allowed (the state then wraps more than once; the rules stay well defined).  Metrics are
+ * int32 without a +inf: no state is ever excluded.
+ * d_frames: int32[F][8], 4-byte aligned:
+ *   [0] c^l(e) of the returned path: the Hamming distance, the Hamming distance over the kept
+ *       bits, or the soft distance    [1] s_0    [2] s_T
+ *   [3] status: 0, 2 or 3 as above; 1 skipped
+ *   [4] hard errors: equal to [0] for hard and punctured frames; soft: the sign disagreements
+ *       of the returned path    [5] counted positions: n*T, the kept bits, or the non-erased values
+ *   [6] laps run    [7] 0
+ * A skipped frame has a zero row of bits and the record {0, -1, -1, 1, 0, 0, 0, 0}.
+ * d_stats: int64[9], written (not accumulated), 8-byte aligned:
+ *   [0] sum of distances  [1] frames decoded (status 0, 2 or 3)  [2] frames skipped
+ *   [3] sum of hard errors  [4] sum of counted  [5] w  [6] frames of status 2
+ *   [7] frames of status 3  [8] sum of laps
+ * All are integer sums, so the result does not depend on the launch shape.
+ * Consistency:
+ *   with I = 1 every frame of status 0 or 3 has the row, [0], [1] and [2] of
+ *   cvd_viterbi_decode_frames(..., CVD_FRAME_ANY, CVD_FRAME_ANY);
+ *   the soft call on values +-A returns the hard call's rows, states, status and laps, with
+ *   [0] = A * errors;
+ *   the punctured call with every keep[c] = 2^n - 1 returns the hard call's result.
+ * CVD_E_INVALID, before the device is touched, cvd_last_error() naming
+ * viterbi_decode_frames_tailbiting (_punctured, _soft), for every case that the frames calls
+ * list except those about the boundary states, and for max_laps outside 0..8.
+ * d_work: cvd_viterbi_tailbiting_workspace_bytes(n, m, T, F, soft) bytes, 16-byte aligned.  0
+ * where the kernel keeps a frame's decision words (T rounded up to 64 steps of max(8, 2^m / 8)
+ * bytes) in LDS: up to 8 KiB of them, T <= 1024 at m <= 6.  Otherwise one frame's decision
+ * words per wave of the launch (at most 8,192 waves, and as many as about 1 GiB holds): per
+ * wave, not per frame, a wave reuses its slice.  The environment variables
+ * CVD_TAILBITE_LDS_BYTES (the LDS limit, at most 32 KiB) and CVD_TAILBITE_WAVES (the wave cap),
+ * read at both calls, are for measurements and tests.  0 at F == 0; < 0 with the error set as
+ * cvd_viterbi_frames_workspace_bytes.  A size of 0 allows a null d_work.  Asynchronous on
+ * `stream`: one launch.  Kernels: csrc/cvd_decode_tailbite.hip. */
+int64_t cvd_viterbi_tailbiting_workspace_bytes(int32_t n, int32_t m, int32_t T, int64_t F, int32_t soft);
+int cvd_viterbi_decode_frames_tailbiting(const cvd_code* code, const void* d_capture, int64_t nbits, int32_t format,
+                                         int64_t start, int64_t stride, const int64_t* d_offsets, int64_t F, int32_t T,
+                                         int32_t max_laps,
+                                         uint32_t* d_bits, int32_t* d_frames, int64_t* d_stats, void* d_work,
+                                         void* stream);
+int cvd_viterbi_decode_frames_tailbiting_punctured(const cvd_code* code, const uint8_t* keep, int32_t period,
+                                                   const void* d_capture, int64_t nbits, int32_t format,
+                                                   int64_t start, int64_t stride, const int64_t* d_offsets, int64_t F,
+                                                   int32_t T, int32_t max_laps,
+                                                   uint32_t* d_bits, int32_t* d_frames, int64_t* d_stats, void* d_work,
+                                                   void* stream);
+int cvd_viterbi_decode_frames_tailbiting_soft(const cvd_code* code, const int8_t* d_soft, int64_t nvals,
+                                              int64_t start, int64_t stride, const int64_t* d_offsets, int64_t F,
+                                              int32_t T, int32_t max_laps,
+                                              uint32_t* d_bits, int32_t* d_frames, int64_t* d_stats, void* d_work,
+                                              void* stream);
 
 /* ---- error-exponent engine (alpha_exponent.py, Eq. 7) ---------------------
  * Joint counts of (metric state i, received word r) along received streams
