@@ -162,6 +162,7 @@ struct ExpArgs {
   uint32_t bfly_even[4];    // k = 1 butterfly kernel: nibble masks of the butterflies with out(j, 0) in {00, 11}
   uint32_t hmask, fmask, fmask4;   // fmask: filter blocks - 1, fmask4 = fmask << 3 (block byte offsets)
   uint32_t ksh, rsh;        // directory slot strides as byte shifts: key (hkey), record (hrow)
+  uint32_t rec_off;         // k1s: byte offset of the dense records (drow) from hkey -- one allocation, 128-B aligned
   int32_t max_probe;
   int32_t slot0;            // row of D_0 = 0
   double lp_unseen;

@@ -620,10 +620,11 @@ void build_hash(cvd_model& Mo) {
   if (const char* e = std::getenv("CVD_BS_LOAD_LOG2")) bload = std::max(1, std::min(5, std::atoi(e)));
   int64_t bcap = 64;
   while (bcap < ((int64_t)1 << bload) * Mo.n_rows) bcap <<= 1;
-  // the kernel addresses the directory, the two-step records and the images by 32-bit byte
-  // offsets: past 4 GiB (over ~2·10^6 rows) the model keeps the nibble tables
+  // the kernel addresses the directory with the dense records behind it (one allocation,
+  // cvd_kernels.hip upload_model), the two-step records and the images by 32-bit byte offsets:
+  // past 4 GiB (over ~2·10^6 rows) the model keeps the nibble tables
   constexpr int kSlotW = 64;   // dwords per directory slot (256 B)
-  if (bcap * 4 * kSlotW > ((int64_t)1 << 32) || Mo.n_rows * 512 > ((int64_t)1 << 32)) Mo.bs = false;
+  if (bcap * 4 * kSlotW + Mo.n_rows * 4 * (int64_t)Mo.h_rsw > ((int64_t)1 << 32) || Mo.n_rows * 512 > ((int64_t)1 << 32)) Mo.bs = false;
   Mo.h_bfilt.clear(); Mo.h_bfilt_lds.clear(); Mo.h_bkey_rows.clear(); Mo.h_bkey_slot.clear(); Mo.h_bdkey.clear();
   Mo.h_bpf.clear();
   Mo.bhcap = 0; Mo.bmax_probe = 0;

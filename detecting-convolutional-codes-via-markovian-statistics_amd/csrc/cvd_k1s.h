@@ -168,38 +168,42 @@ __device__ __forceinline__ void bs_lt_add(double& lr, const double* s_lt, double
 // row (a filter-positive candidate that matches) simply do not use it.  So the filter read
 // has the rest of the step and half of the next one to land, and the key and record loads
 // the second word's ACS plus the hash.
+// One record load per step (kBsOneLoad, BsCursor::mid) in the kernels that read the filter from
+// L2 (the pre-filter and plain variants; p >= 0.05 of the sweep, 0.7-2.8% shorter launches).  The
+// LDS-filter variants (p = 0.01, 0.02; separate builds, CVD_K1B_LDSF) keep the two sites -- a
+// known row's dense record requested after the resolve for the next word, a candidate's at mid():
+// their H1 lanes are on a row at 94% of the steps, few steps hold both kinds, and the merged
+// form's address selection cost them more VALU than the load it saved (p = 0.01 1,278 -> 1,311
+// ms, VALU per wave-step 115.7 -> 119.1, VMEM 1.28 -> 1.12; DESIGN.md §2, profiles/record_load)
+#if CVD_K1B_LDSF
+constexpr bool kBsOneLoad = false;
+#else
+constexpr bool kBsOneLoad = true;
+#endif
 struct BsCursor {
   int32_t slot, pnx;
   uint32_t hs, hsn, fb, fw, fb1, fw1, pc;   // hs: home slot of D_{t-1}'s lookup, hsn: of D_t's
-  // Inert remnants of removed variants (pfpos: the pre-filter verdict carried to the resolve;
-  // h2wave: a timing ablation; vhmask / vfmask4: the lookup masks as VGPR copies; half: the
-  // two-step records' state, still cleared in start and resolve).  Nothing reads them and no
-  // instruction comes from them, but without the default initialisers and the two stores the
-  // compiler emits the six-step loop's same instructions in another order with other registers.
-  // They stay so that the kernels' code is byte for byte what was measured, and
-  // go with the next change to the loop that is measured on its own.  (Their places among the
-  // live fields matter in the same way.)
   bool cand;
-  bool pfpos = true;
-  bool h2wave = false;
   double plp;
   uint32_t pkey[8];
-  uint32_t vhmask = 0u, vfmask4 = 0u;
-  uint32_t half;
-  // entry rn (16 B {log P̂1, successor row, T_ref count c}) of learned row s, dense records
+  // entry rn (16 B {log P̂1, successor row, T_ref count c}) of learned row s, dense records:
+  // walk mode's one-step record, and the lockstep loop's without kBsOneLoad
   // (every k1s offset is a 32-bit byte offset from the table's base: the host keeps the
   // bit-sliced tables under 4 GiB)
   __device__ void prefetch_row(const ExpArgs& a, int32_t s, uint32_t rn) {
     uint32_t o;
     asm("v_lshl_add_u32 %0, %1, 6, %2" : "=v"(o) : "v"((uint32_t)s), "v"(rn));
-    const uint4 v = ld_off<uint4>(a.drow, o);
+    take(ld_off<uint4>(a.drow, o));
+  }
+  __device__ void take(const uint4& v) {
     pc = v.w;
     pnx = (int32_t)v.z;
     plp = __hiloint2double((int)v.y, (int)v.x);
   }
-  __device__ void start(const ExpArgs& a, uint32_t r0) {
-    slot = a.slot0; hs = 0u; hsn = 0u; fb = 0u; fw = 0u; fb1 = 0u; fw1 = 0u; cand = false; pc = 1u; half = 0u;
-    prefetch_row(a, slot, r0);
+  // (no record is loaded here: with kBsOneLoad every step's is requested at its mid(), without
+  // it the caller requests row slot0's for the first word)
+  __device__ void start(const ExpArgs& a) {
+    slot = a.slot0; pnx = -1; hs = 0u; hsn = 0u; fb = 0u; fw = 0u; fb1 = 0u; fw1 = 0u; cand = false; pc = 1u; plp = 0.0;
   }
   // ordering fences (RowCursor::fence): the waits for the loads issued a step / half a step
   // earlier land after the ACS work the dependency names.  fence_mid: the filter words (the
@@ -218,18 +222,46 @@ struct BsCursor {
     const uint4 u = ld_off<uint4>(base, o), v = ld_off<uint4>(base, o + 16u);
     k[0] = u.x; k[1] = u.y; k[2] = u.z; k[3] = u.w; k[4] = v.x; k[5] = v.y; k[6] = v.z; k[7] = v.w;
   }
-  // filter positive: the home slot's image of phase PH and its record for word r
-  template <int PH>
+  // The record {log P̂1, successor, c} of this step (word r), one load for the wave (kRow): a
+  // filter-positive candidate's from its home slot, a known row's dense one -- which lies behind
+  // the directory in the same allocation, at a.rec_off -- and for a lane that needs neither
+  // one line that such lanes share (as filter word 0 in hash_ahead).  A candidate has
+  // slot == -2, so the two kinds never meet in a lane; loaded apart, a wave that holds one lane
+  // of each kind issued two instructions per step, and the step's time follows their count
+  // (DESIGN.md §2).  No divergent branch around the load; a wave without a lane of either kind
+  // (most steps of an H2 wave) skips it by a wave-uniform test.  A candidate also loads the home
+  // slot's image of phase PH.
+  // (!kRow, walk mode's ACS steps: candidates only, a lane that has just left its rows keeps
+  // the record walk_prefetch loaded; so without kBsOneLoad, where next_row() requests a row's)
+  template <int PH, bool kRow>
   __device__ void mid(const ExpArgs& a, uint32_t r) {
     // (two v_bitop3: the compiler's form was six VALU)
     cand = slot == -2 && cvd::bs_bop3<cvd::kTtAndNotOr>(fb1, fw1, cvd::bs_bop3<cvd::kTtAndNotOr>(fb, fw, 0u)) == 0u;
-    if (cand) {
+    if constexpr (kRow && kBsOneLoad) {
+      bs_u32x4 v;
+      if (__ballot(cand || slot >= 0) != 0u) {
+        // both records as 64-B units from the base: a slot's at 4 hs + 3 (kBsRecOff = 3 * 64),
+        // row s's at rec_off / 64 + s; so four VALU to the address: shift-or, add, select, and
+        // one shift-add with the word offset.  (A lane that is neither has slot = -1 or -2 and
+        // reads the directory's last 128 bytes, a line such lanes share; nothing uses it.)
+        static_assert(kBsRecOff == 192u && kBsSlotShift == 6, "a slot's records are its fourth 64-B unit");
+        uint32_t uc, o;
+        asm("v_lshl_or_b32 %0, %1, 2, 3" : "=v"(uc) : "v"(hs));
+        const uint32_t ud = (uint32_t)slot + (a.rec_off >> 6);
+        asm("v_lshl_add_u32 %0, %1, 6, %2" : "=v"(o) : "v"(cand ? uc : ud), "v"(r));
+        v = ld_off<bs_u32x4>(a.hkey, o);
+      } else {
+        // (no lane reads the record: any contents of the four registers will do, and saying so
+        // keeps the last step's record from living on through the skipped load, which made the
+        // loaded one a copy that is waited for at once)
+        asm volatile("" : "=v"(v));
+      }
+      take(make_uint4(v.x, v.y, v.z, v.w));
+      if (cand) load_image(a.hkey, slot_off(hs) + bs_img_off<PH>(), pkey);
+    } else if (cand) {
       const uint32_t so = slot_off(hs);
       load_image(a.hkey, so + bs_img_off<PH>(), pkey);
-      const uint4 v = ld_off<uint4>(a.hkey, so + kBsRecOff + r);
-      pc = v.w;
-      pnx = (int32_t)v.z;
-      plp = __hiloint2double((int)v.y, (int)v.x);
+      take(ld_off<uint4>(a.hkey, so + kBsRecOff + r));
     }
   }
   __device__ static bool same(const uint32_t (&k)[8], const uint32_t (&R)[2][4]) {
@@ -252,10 +284,8 @@ struct BsCursor {
     // -> 3,069 cycles per six steps, profiles/r06ad); a candidate implies slot == -2, so it needs
     // no test of the row being known
     const uint32_t m = (uint32_t)(slot >> 31);   // ~0: D_{t-1}'s row is not known
-    double lpv = lpu;   // (these two initial values are overwritten below; as `half`, they keep the
-    int32_t ns = -2;    // compiled loop as measured)
-    ns = (int32_t)cvd::bs_bop3<cvd::kTtSel>(m, (uint32_t)-2, (uint32_t)pnx);
-    lpv =
+    int32_t ns = (int32_t)cvd::bs_bop3<cvd::kTtSel>(m, (uint32_t)-2, (uint32_t)pnx);
+    double lpv =
         __hiloint2double((int)cvd::bs_bop3<cvd::kTtSel>(m, (uint32_t)__double2hiint(lpu), (uint32_t)__double2hiint(plp)),
                          (int)cvd::bs_bop3<cvd::kTtSel>(m, (uint32_t)__double2loint(lpu), (uint32_t)__double2loint(plp)));
     if (cand) {
@@ -281,7 +311,6 @@ struct BsCursor {
       }
     }
     slot = ns;
-    half = 0u;
     return lpv;
   }
   // D_t (planes N at phase PH) is known, D_{t-1}'s lookup not yet resolved: a lane whose
@@ -327,23 +356,24 @@ struct BsCursor {
     fw = f.x;
     fw1 = f.y;
   }
-  // after the resolve: a known row's dense record for the next word (kRow; walk mode loads
-  // its own), and D_t's home slot becomes the pending lookup's
-  template <bool kRow = true>
-  __device__ void next(const ExpArgs& a, uint32_t rn) {
-    if (kRow && slot >= 0) prefetch_row(a, slot, rn);
-    hs = hsn;
+  // after the resolve: D_t's home slot becomes the pending lookup's
+  __device__ void next() { hs = hsn; }
+  // the same with two load sites (the lockstep loop without kBsOneLoad): first a known row's
+  // dense record for the next word rn
+  __device__ void next_row(const ExpArgs& a, uint32_t rn) {
+    if (slot >= 0) prefetch_row(a, slot, rn);
+    next();
   }
 };
 
 // one bit-sliced step of a lane: D_{t-1} = R (phase PH) -> N (phase PH + 1) under word rr,
-// the filter-positive loads issued between the two words' ACS
-template <int PH, bool kUni>
+// the record and filter-positive loads issued between the two words' ACS
+template <int PH, bool kUni, bool kRow = true>
 __device__ __forceinline__ void bs_step(const ExpArgs& a, BsCursor& cur, const uint32_t (&R)[2][4], uint32_t rr,
                                         uint32_t (&N)[2][4], uint32_t& c, bool& one) {
   bs_core_tab<PH, kUni>(R, rr, N, c, one, [&](uint32_t dep) {
     cur.fence_mid(dep);            // dep: the first word's ACS result
-    cur.template mid<PH>(a, rr);
+    cur.template mid<PH, kRow>(a, rr);
   });
   cur.template hash_ahead<(PH + 1) % 6>(a, N);   // D_t's filter read before D_{t-1}'s loads are waited for
   cur.fence_resolve(N[1][3]);                    // N[1][3] depends on the whole ACS
@@ -432,12 +462,12 @@ __device__ __forceinline__ void k1s_walk(const ExpArgs& a, int64_t qwave, uint64
     const uint32_t rr = word_param(word_at() & 3u);
     uint32_t Nn[2][4], c;
     bool one;
-    bs_step<PH, kUni>(a, cur, R, rr, Nn, c, one);
+    bs_step<PH, kUni, false>(a, cur, R, rr, Nn, c, one);
     if (mode == kWalkAcs) {
       lp += cur.template resolve<PH>(a, R, rr, a.lp_unseen);   // Pd_plotter.py:115, T = P̂1
       bs_lt_add(lr, s_lt, lt1, c, one);   // Pd_plotter.py:115, T = T_ref(1/2)
       advance();
-      cur.template next<false>(a, 0u);
+      cur.next();
       if (finished()) {
         mode = kWalkDone;
         cur.slot = -1;
@@ -633,8 +663,13 @@ __device__ __forceinline__ void k1s_wave(const ExpArgs& a, int64_t gw, const dou
     uint32_t cw = pick(wi), nw = pick(wi + 1);
     uint32_t sh = 0u;
     BsCursor cur;
-    cur.start(a, word_param(cw & 3u));
+    cur.start(a);
+    if constexpr (!kBsOneLoad) cur.prefetch_row(a, cur.slot, word_param(cw & 3u));
     const double lt1 = a.ltref[1];   // (= s_lt[1]: the term of a wave-step without a suspect lane)
+    // (rn: the next step's word, for the second load site.  With kBsOneLoad nothing reads it and
+    // its extraction at the call sites emits nothing, but without those dead expressions the
+    // compiler gives the pre-filter kernel's loop the same instructions with other registers in
+    // another order; they stay, so that the loop is the one that was measured)
     auto step = [&](auto phc, uint32_t rr, uint32_t rn) {
       constexpr int PH = decltype(phc)::value;
       uint32_t Nn[2][4], c;
@@ -646,7 +681,8 @@ __device__ __forceinline__ void k1s_wave(const ExpArgs& a, int64_t gw, const dou
       for (int r = 0; r < 2; ++r)
 #pragma unroll
         for (int i = 0; i < 4; ++i) R[r][i] = Nn[r][i];
-      cur.next(a, rn);
+      if constexpr (kBsOneLoad) cur.next();
+      else cur.next_row(a, rn);
     };
     int64_t t = t_begin;
     int grp = 0, dec = 0;
@@ -688,8 +724,6 @@ __device__ __forceinline__ void k1s_wave(const ExpArgs& a, int64_t gw, const dou
       }
     }
     // last 1-5 steps
-    const int ntail = (int)(t_end - t);   // (unused: as BsCursor's `half`, keeps the compiled loop as measured)
-    (void)ntail;
     if (t < t_end) {
       if (ck && t == t_sum) {   // (a last chunk of fewer than six steps)
         ck_store(a, qwave, ck_j, 0u, R);

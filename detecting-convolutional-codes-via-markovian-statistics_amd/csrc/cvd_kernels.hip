@@ -1575,13 +1575,17 @@ __global__ __launch_bounds__(kBlock) void dir_scatter_kernel(const uint32_t* row
   dir[(size_t)slots[i] * (size_t)w + (size_t)k] = rows[idx];
 }
 
+// `tail`: words copied behind the directory into the same allocation (the bit-sliced kernel's
+// dense records, at ExpArgs::rec_off).
 int dev_directory(uint32_t*& d, const std::vector<uint32_t>& rows, const std::vector<uint32_t>& slots, int64_t cap,
-                  int32_t w, uint32_t fill) {
+                  int32_t w, uint32_t fill, const std::vector<uint32_t>* tail = nullptr) {
   if (rows.empty() || cap <= 0) return CVD_OK;
   const int64_t n = (int64_t)slots.size();
   if ((int64_t)rows.size() != n * w) { set_error("directory rows / slots mismatch"); return CVD_E_INVALID; }
-  HIP_CHECK(hipMalloc(&d, (size_t)cap * (size_t)w * sizeof(uint32_t)));
+  const size_t ntail = tail ? tail->size() : 0u;
+  HIP_CHECK(hipMalloc(&d, ((size_t)cap * (size_t)w + ntail) * sizeof(uint32_t)));
   HIP_CHECK(hipMemsetD32(d, (int)fill, (size_t)cap * (size_t)w));
+  if (ntail) HIP_CHECK(hipMemcpy(d + (size_t)cap * (size_t)w, tail->data(), ntail * sizeof(uint32_t), hipMemcpyHostToDevice));
   uint32_t *dr = nullptr, *ds = nullptr;
   HIP_CHECK(hipMalloc(&dr, rows.size() * sizeof(uint32_t)));
   HIP_CHECK(hipMalloc(&ds, slots.size() * sizeof(uint32_t)));
@@ -2025,6 +2029,9 @@ static unsigned rtc_dyn_lds(const cvd_model& M) {
   return 0u;
 }
 
+// dwords of the bit-sliced directory, behind which its allocation holds the dense records
+static size_t bs_rec_words(const cvd_model& M) { return (size_t)M.bhcap << cvd_dev::kBsSlotShift; }
+
 // The explicit path's launch arguments of one model over one stream buffer.
 static ExpArgs exp_args(const cvd_model& M, int which, const uint32_t* d_r, int64_t N, int64_t nseq, int64_t n_h1,
                         double* d_sums, int64_t* d_counts, uint8_t* d_trace, const uint32_t* bmp, bool early) {
@@ -2039,6 +2046,9 @@ static ExpArgs exp_args(const cvd_model& M, int which, const uint32_t* d_r, int6
   // (no separate record array), at dword nw of each key slot; bit-sliced: 64-dword slots
   // whose layout the kernel knows (cvd_k1s.h)
   a.hrow = bs ? M.d_bkey : M.d_hrow ? M.d_hrow : M.d_hkey + nib_words(M.dec.m);
+  // (k1s reads a known row's dense record and a candidate's slot record with one load, by
+  // 32-bit byte offsets from hkey: upload_model puts the dense records behind the directory)
+  a.rec_off = bs ? (uint32_t)(bs_rec_words(M) * sizeof(uint32_t)) : 0u;
   a.ksh = bs ? 8u : (uint32_t)__builtin_ctz((unsigned)(4 * M.h_ssw));
   a.rsh = bs ? 8u : M.d_hrow ? (uint32_t)__builtin_ctz((unsigned)(4 * M.h_rsw)) : a.ksh;
   a.bmp = bmp; a.slot0 = M.slot0;
@@ -2409,14 +2419,17 @@ int cvd::upload_model(cvd_model& M, int device) {
     if ((rc = dev_copy(M.d_filt_lds, M.h_filt_lds))) return rc;
     if ((rc = dev_directory(M.d_hkey, M.h_key_rows, M.h_key_slot, M.hcap, M.h_ssw, kEmptyKey))) return rc;
     if ((rc = dev_directory(M.d_hrow, M.h_row_rows, M.h_key_slot, M.hcap, M.h_rsw, 0u))) return rc;
-    if ((rc = dev_copy(M.d_drow, M.h_drow))) return rc;
     if ((rc = dev_copy(M.d_dkey, M.h_dkey))) return rc;
     if ((rc = dev_copy(M.d_t2, M.h_t2))) return rc;
     if ((rc = dev_copy(M.d_t2c, M.h_t2c))) return rc;
     if ((rc = dev_copy(M.d_vtab, M.h_vtab))) return rc;
     if ((rc = dev_copy(M.d_bfilt, M.h_bfilt))) return rc;
     if ((rc = dev_copy(M.d_bfilt_lds, M.h_bfilt_lds))) return rc;
-    if ((rc = dev_directory(M.d_bkey, M.h_bkey_rows, M.h_bkey_slot, M.bhcap, 1 << cvd_dev::kBsSlotShift, 0u))) return rc;
+    // the dense records: behind the bit-sliced directory where the model has one (build_hash
+    // keeps the two under 4 GiB together), d_drow then a pointer into that allocation
+    if ((rc = dev_directory(M.d_bkey, M.h_bkey_rows, M.h_bkey_slot, M.bhcap, 1 << cvd_dev::kBsSlotShift, 0u, &M.h_drow))) return rc;
+    if (M.d_bkey) M.d_drow = M.d_bkey + bs_rec_words(M);
+    else if ((rc = dev_copy(M.d_drow, M.h_drow))) return rc;
     if ((rc = dev_copy(M.d_bdkey, M.h_bdkey))) return rc;
     if ((rc = dev_copy(M.d_bpf, M.h_bpf))) return rc;
     if ((rc = dev_copy(M.d_bmp, M.bmp))) return rc;
@@ -2502,6 +2515,7 @@ void cvd::free_model_device(cvd_model& M) {
   int cur = 0;
   (void)hipGetDevice(&cur);
   (void)hipSetDevice(M.device);
+  if (M.d_bkey) M.d_drow = nullptr;   // (part of d_bkey's allocation)
   void* ptrs[] = {M.d_rec, M.d_logp1, M.d_ltref, M.d_filt, M.d_filt_lds, M.d_hkey, M.d_hrow, M.d_drow, M.d_dkey, M.d_t2,
                   M.d_t2c, M.d_vtab, M.d_bmp,
                   M.d_bmk1, M.d_bfly, M.d_err, M.d_bfilt, M.d_bfilt_lds, M.d_bkey, M.d_bdkey, M.d_bpf};
