@@ -36,7 +36,7 @@
   ... decode --code C --input FILE [--format bytes|lsb|msb|soft] [--nbits B] [--start S] [--T T]
              [--out-bits FILE.npy] [--puncture SPEC [--sync T0]]
              [--frame T [--frame-count F] [--frame-stride B | --frame-offsets FILE.npy]
-              [--start-state S|any] [--end-state S|any] | [--tail-biting [--laps I]]]
+              [--start-state S|any] [--end-state S|any] | [--tail-biting [--laps I]]] [--llr]
       (nothing in the reference) -- what was sent: the hard-decision Viterbi decoder of the
       k = 1 code C over the capture from bit S (cvd_viterbi_decode: the Eq. 4-5 recursion with
       its survivor decisions kept, exact whatever the block split); writes the decoded bits to
@@ -76,6 +76,13 @@
       CSV gains the column laps and status reads 0 tail-biting best path, 1 skipped, 2 best
       tail-biting survivor of the last lap, 3 no tail-biting survivor (start_state !=
       end_state); the summary adds the numbers of such frames and the mean laps.
+      --frame T --format soft --llr: soft output (cvd_viterbi_decode_frames_llr): beside
+      decoded.npy the run writes <save-dir>/llr.npy (int16 [F, T]), the max-log-MAP value of every
+      bit: the cost of the best path with that bit 0 minus that of the best path with it 1,
+      positive for a 1, in the units of the input, +-32767 where the other value has no path (the
+      tail of a terminated frame).  The CSV's columns are then frame, offset, status, distance,
+      zeros (undecided bits), weakest (the smallest |value| of the frame), saturated, end_state.
+      An error without --frame, without --format soft, with --tail-biting or with --puncture.
 
 Codes: the BASELINE configurations (m2, m6, r23_m4), the demo presets (example:1,
 example:2, demo_script.py:35-52), or oct:G0,G1[,G2] -- k = 1 generators in octal (MSB =
@@ -93,7 +100,7 @@ import sys
 
 from . import (CONFIG_CODES, DEFAULTS, EXAMPLE_CODES, compute_error_exponent, default_template,
                decode_capture, decode_capture_punctured, decode_capture_soft, decode_frames, decode_frames_soft,
-               decode_frames_tailbiting, decode_frames_tailbiting_soft,
+               decode_frames_llr, decode_frames_tailbiting, decode_frames_tailbiting_soft,
                find_parity_checks,
                learn_transition_tensor, octal_to_taps, parity_experiment, parity_vector_to_equation, parity_vectors,
                puncture_pattern, punctured_bits, run_experiment, scan_capture, sync_punctured, sync_punctured_soft)
@@ -240,6 +247,10 @@ def parser():
                         "(not with --start-state or --end-state)")
     d.add_argument("--laps", type=int, default=None, metavar="I",
                    help="with --tail-biting: at most I laps over a frame (1..8, default 4)")
+    d.add_argument("--llr", action="store_true",
+                   help="with --frame and --format soft: also write llr.npy, a max-log-MAP value per bit "
+                        "(not with --tail-biting or --puncture)")
+    d.add_argument("--out-llr", default=None, help="with --llr: the .npy of values (default <save-dir>/llr.npy)")
     d.set_defaults(states_given=False)
 
     c = sub.add_parser("compare", help="P_err figures of both detectors (plots_compare.py)")
@@ -292,6 +303,17 @@ def parse_args(argv=None):
                 ap.error("decode: --tail-biting does not go with --start-state or --end-state: neither state is known")
         if a.laps is not None and not a.tail_biting:
             ap.error("decode: --laps needs --tail-biting")
+        if a.llr:
+            if a.frame is None:
+                ap.error("decode: --llr needs --frame")
+            if a.format != "soft":
+                ap.error("decode: --llr needs --format soft")
+            if a.tail_biting:
+                ap.error("decode: --llr does not go with --tail-biting")
+            if a.puncture is not None:
+                ap.error("decode: --llr does not take --puncture")
+        elif a.out_llr is not None:
+            ap.error("decode: --out-llr needs --llr")
     return a
 
 
@@ -432,6 +454,7 @@ def cmd_identify(a):
 DECODE_COLUMNS = ["T", "errors", "ber", "start_state", "end_state", "blocks", "forward_reruns", "trace_fixups"]
 FRAME_COLUMNS = ["frame", "offset", "status", "distance", "errors", "counted", "start_state", "end_state"]
 TAILBITING_COLUMNS = FRAME_COLUMNS + ["laps"]
+LLR_COLUMNS = ["frame", "offset", "status", "distance", "zeros", "weakest", "saturated", "end_state"]
 
 
 def cmd_decode_frames(a, n, m, g1):
@@ -449,7 +472,7 @@ def cmd_decode_frames(a, n, m, g1):
         hard, soft = decode_frames_tailbiting, decode_frames_tailbiting_soft
     else:
         kw.update(start_state=a.start_state, end_state=a.end_state)
-        hard, soft = decode_frames, decode_frames_soft
+        hard, soft = decode_frames, decode_frames_llr if a.llr else decode_frames_soft
     try:
         if a.format == "soft":
             res = soft(n, m, g1, load_soft_capture(a.input, a.nbits), a.frame, **kw)
@@ -464,10 +487,25 @@ def cmd_decode_frames(a, n, m, g1):
         offsets = a.start + stride * np.arange(res["F"], dtype=np.int64)
     out = a.out or os.path.join(a.save_dir, "decode_frames.csv")
     out_bits = a.out_bits or os.path.join(a.save_dir, "decoded.npy")
-    for path in (out, out_bits):
+    out_llr = (a.out_llr or os.path.join(a.save_dir, "llr.npy")) if a.llr else None
+    for path in (out, out_bits) + ((out_llr,) if a.llr else ()):
         os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     with open(out_bits, "wb") as f:             # (np.save would append .npy to another suffix)
         np.save(f, res["bits"].cpu().numpy())
+    if a.llr:
+        with open(out_llr, "wb") as f:
+            np.save(f, res["llr"].cpu().numpy())
+        with open(out, "w", newline="") as f:
+            wr = csv.writer(f)
+            wr.writerow(LLR_COLUMNS)
+            for i, r in enumerate(frames.tolist()):
+                wr.writerow([i, int(offsets[i]), r[3], r[0], r[1], r[4], r[5], r[2]])
+        print(f"Decoded {res['decoded']} frames of {res['T']} steps ({res['skipped']} skipped): distance "
+              f"{res['total_distance']}, {res['total_zeros']} undecided bits, {res['total_saturated']} saturated")
+        print("Saved bits to", out_bits, f"({res['F']} rows of {res['bits'].shape[1]} bytes)")
+        print("Saved values to", out_llr, f"({res['F']} rows of {res['T']} int16)")
+        print("Saved results to", out)
+        return 0
     with open(out, "w", newline="") as f:
         wr = csv.writer(f)
         wr.writerow(TAILBITING_COLUMNS if a.tail_biting else FRAME_COLUMNS)

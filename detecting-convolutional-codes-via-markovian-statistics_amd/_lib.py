@@ -191,6 +191,13 @@ EXPORTS = {
                                                                  ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32,
                                                                  ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
                                                                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "cvd_viterbi_llr_workspace_bytes": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                                         ctypes.c_int64]),
+    "cvd_viterbi_decode_frames_llr": (ctypes.c_int, [ctypes.POINTER(cvd_code), ctypes.c_void_p, ctypes.c_int64,
+                                                     ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
+                                                     ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
+                                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                     ctypes.c_void_p, ctypes.c_void_p]),
     "cvd_count_transitions": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
                                              ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
     "cvd_chernoff_build": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,

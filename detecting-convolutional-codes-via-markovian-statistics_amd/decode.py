@@ -576,3 +576,64 @@ def decode_frames_tailbiting_soft(n, m, gen, soft, T, F=None, start=0, stride=No
     cap, nvals = _soft_buffer(soft, dev)
     return _tailbiting("decode_frames_tailbiting_soft", "cvd_viterbi_decode_frames_tailbiting_soft", (code.c,), (), cap,
                        nvals, n, m, T, n * T, F, start, stride, offsets, max_laps, True, dev)
+
+
+# ─────────────────────────── soft output per bit ────────────────────────────
+
+LLR_SATURATED = 32767    # include/cvd.h: |L_t| of a step whose other input value has no path
+
+
+def decode_frames_llr(n, m, gen, soft, T, F=None, start=0, stride=None, offsets=None, start_state=0, end_state=0,
+                      device=None):
+    """cvd_viterbi_decode_frames_llr: decode_frames_soft with a max-log-MAP value per bit.  The
+    frames of the soft capture `soft` (int8, as decode_capture_soft takes it; hard bits go through
+    soft_from_bits) are placed as decode_frames places them; start, stride and offsets count
+    values.  L_t = (cost of the best path with u_t = 0) - (cost of the best path with u_t = 1),
+    positive for a 1, in the units of the input; +-32767 where the other value has no path (the
+    tail of a terminated frame).
+    Returns a dict: llr (device int16 [F, T], a view of the rows padded to 32 w values), bits
+    (device uint8 [F, 4w], w = ceil(T/32): bit t = [L_t > 0]), frames (device int32 [F, 6]) and the
+    views of its columns distance (decode_frames_soft's), zeros (#{t : L_t = 0}), end_states,
+    status (0 decoded, 1 skipped), weakest (min |L_t| over the unsaturated steps; 32767 if none),
+    saturated (#{t : |L_t| = 32767}); T, F, words (w), decoded, skipped, total_distance,
+    total_zeros and total_saturated."""
+    dev = device if isinstance(device, torch.device) else _require_gpu(device)
+    n, m, T = int(n), int(m), int(T)
+    code = as_code(gen, m, 1, n)
+    cap, nvals = _soft_buffer(soft, dev)
+    if not 1 <= T <= FRAME_MAX_T:
+        raise ValueError(f"T = {T}: a frame has 1..{FRAME_MAX_T} steps")
+    ss, es = _frame_state("start_state", start_state, m), _frame_state("end_state", end_state, m)
+    if ss >= 0 and es >= 0 and T < m:
+        raise ValueError(f"T = {T} < m = {m}: with both states fixed the end state is not reachable")
+    w = (T + 31) // 32
+    off, F, start, stride = _frame_placement(nvals, n * T, w, F, start, stride, offsets, dev)
+    L = _lib.lib()
+    call = L.cvd_viterbi_decode_frames_llr
+    wbytes = int(L.cvd_viterbi_llr_workspace_bytes(n, m, T, F))
+    if wbytes < 0:
+        # the decoder itself names an unsupported code shape
+        _lib.check(call(code.c, None, 0, 0, 1, None, 0, T, ss, es, None, None, None, None, None, None))
+        _lib.check(wbytes)
+    with torch.cuda.device(dev):
+        llr = torch.empty((F, 32 * w), dtype=torch.int16, device=dev)
+        bits = torch.empty((F, 4 * w), dtype=torch.uint8, device=dev)
+        frames = torch.empty((F, 6), dtype=torch.int32, device=dev)
+        s = [0, 0, 0, 0, 0, w]
+        if F:
+            free = torch.cuda.mem_get_info(dev)[0]
+            if wbytes > free:
+                raise MemoryError(f"decode_frames_llr: the workspace of {F} frames of T = {T} steps (m = {m}) is "
+                                  f"{wbytes} bytes, {free} bytes of device memory are free: decode the frames in pieces")
+            stats = torch.zeros(6, dtype=torch.int64, device=dev)
+            work = torch.empty(wbytes, dtype=torch.uint8, device=dev) if wbytes else None
+            _lib.check(call(code.c, ctypes.c_void_p(cap.data_ptr()), nvals, start, stride,
+                            ctypes.c_void_p(off.data_ptr()) if off is not None else None, F, T, ss, es,
+                            ctypes.c_void_p(llr.data_ptr()), ctypes.c_void_p(bits.data_ptr()),
+                            ctypes.c_void_p(frames.data_ptr()), ctypes.c_void_p(stats.data_ptr()),
+                            ctypes.c_void_p(work.data_ptr()) if work is not None else None, _stream_ptr()))
+            s = stats.cpu().tolist()     # synchronises: cap, off and work may be freed on return
+    return {"llr": llr[:, :T], "bits": bits, "frames": frames, "distance": frames[:, 0], "zeros": frames[:, 1],
+            "end_states": frames[:, 2], "status": frames[:, 3], "weakest": frames[:, 4], "saturated": frames[:, 5],
+            "T": T, "F": F, "decoded": int(s[1]), "skipped": int(s[2]), "total_distance": int(s[0]),
+            "total_zeros": int(s[3]), "total_saturated": int(s[4]), "words": int(s[5])}

@@ -761,6 +761,70 @@ int cvd_viterbi_decode_frames_tailbiting_soft(const cvd_code* code, const int8_t
                                               uint32_t* d_bits, int32_t* d_frames, int64_t* d_stats, void* d_work,
                                               void* stream);
 
+/* ---- soft output: max-log-MAP values per bit of framed soft captures (nothing in the reference) ----
+ * Every decoder above ends in hard information bits and one distance per frame.  An outer code
+ * (Reed-Solomon with erasures, a CRC-aided list or Chase stage), the ranking of the candidates of
+ * a blind search, or the choice of which frames to trust needs to know how sure each bit is.  This
+ * call is cvd_viterbi_decode_frames_soft with a value L_t per step beside the bit: the difference
+ * between the best path with u_t = 0 and the best path with u_t = 1, in the units of the input.
+ * Inherited unchanged from cvd_viterbi_decode_frames_soft: the code shapes (k = 1, n in {2, 3},
+ * 1 <= m <= 8, else CVD_E_UNSUPPORTED), the int8 capture (-128 read as -127, 0 an erasure, 16-byte
+ * alignment and readability, nothing at or past nvals rounded up to 16 bytes is read), cost(out, t),
+ * the placement of the frames (stride mode, or d_offsets with skipped frames), 1 <= T <=
+ * CVD_VITERBI_FRAME_MAX_T, CVD_FRAME_ANY, T >= m when both states are fixed, F*w < 2^31 with
+ * w = ceil(T/32), and F == 0 (CVD_OK, nothing written).
+ * The recursion of one frame, over the integers extended by +inf (a sequential decoder written
+ * from this text reproduces the result bit for bit); ps_b and out as in cvd_viterbi_decode, S = 2^m:
+ *   alpha_0 = D_0 of the frames contract (0 everywhere, or 0 at start_state and +inf elsewhere);
+ *   alpha_{t+1}(s') = min_b [alpha_t(ps_b) + cost(out(ps_b, s' & 1), t)];
+ *   beta_T(s) = 0 for every s if end_state is CVD_FRAME_ANY, else beta_T(e) = 0, +inf elsewhere;
+ *   beta_t(s) = min_u [cost(out(s, u), t) + beta_{t+1}(((s << 1) | u) & (S - 1))];
+ *   M_u(t) = min over the states s' with s' & 1 = u of [alpha_{t+1}(s') + beta_{t+1}(s')], u in
+ *   {0, 1}: alpha_{t+1} is already the minimum over the predecessors, so this is the cost of the
+ *   best whole path whose input at step t is u.
+ * The value of step t:
+ *   L_t = M_0(t) - M_1(t): positive when a 1 is more likely, the sign convention and the units of
+ *   the input values; L_t = +32767 if M_0(t) = +inf, L_t = -32767 if M_1(t) = +inf.
+ * Both minima are never infinite together (some path satisfies the boundary conditions).  A finite
+ * L_t obeys |L_t| <= 127*n*(m+1) <= 3429 (flip u_t on the best path and rejoin it m steps later),
+ * so int16 holds every value and +-32767 is unambiguous.  With end_state fixed exactly the steps
+ * t >= T - m are saturated, with the sign that bit T-1-t of e gives (the tail is known); with
+ * end_state CVD_FRAME_ANY nothing is saturated.  Any implementation constant above every finite
+ * metric serves as +inf; the frames calls' 2^28 does if two of them may be added.
+ * d_llr: F rows of 32*w int16, 16-byte aligned; value t of row f is L_t, values at or past T are 0.
+ * d_bits: as the frames calls; bit t of row f = [L_t > 0].
+ * d_frames: int32[F][6], 4-byte aligned:
+ *   [0] the distance min(M_0(t), M_1(t)): the same for every t, and cvd_viterbi_decode_frames_soft's [0]
+ *   [1] #{t : L_t = 0}, the steps the decoder cannot decide
+ *   [2] s_T by the frames rule: e, or the lowest-index state of minimal alpha_T
+ *   [3] status: 0 decoded, 1 skipped
+ *   [4] min |L_t| over the unsaturated t, the frame's weakest bit; 32767 if there is none
+ *   [5] #{t : |L_t| = 32767}
+ * A skipped frame has zero rows of values and bits and the record {0, 0, -1, 1, 0, 0}.
+ * d_stats: int64[6], written (not accumulated), 8-byte aligned:
+ *   [0] sum of distances  [1] frames decoded  [2] frames skipped  [3] sum of [1]  [4] sum of [5]  [5] w
+ * All sums are integer sums, so the result does not depend on the launch shape.
+ * Consistency: wherever L_t != 0, bit t equals the bit of cvd_viterbi_decode_frames_soft on the
+ * same arguments (L_t > 0 means that every best path has u_t = 1); [0] and [2] equal that call's.
+ * CVD_E_INVALID, before the device is touched, cvd_last_error() naming viterbi_decode_frames_llr,
+ * for every case that cvd_viterbi_decode_frames_soft lists, and for a null or misaligned d_llr.
+ * d_work: cvd_viterbi_llr_workspace_bytes(n, m, T, F) bytes, 16-byte aligned.  The kernel does not
+ * keep alpha for every step: it keeps the vector at every 32nd step, 2^m int32 each, and
+ * recomputes a segment of 32 steps before beta runs back through it; the first segment starts
+ * from D_0 and the last one is not computed twice.  0 where T <= 64.  Otherwise ceil(T/32) - 2
+ * vectors per wave of the launch (at most 8,192 waves, and as many as about 1 GiB holds): per
+ * wave, not per frame, a wave reuses its slice.  The environment variable
+ * CVD_LLR_WAVES (the wave cap), read at both calls, is for measurements and tests.  (The segment
+ * length is a compile-time constant: there is no CVD_LLR_SEG.)  0 at F == 0; < 0 with the error
+ * set for n, m outside the shapes, T outside 1..65536 or F < 0.  A size of 0 allows a null d_work.
+ * Asynchronous on `stream`: one launch.  Kernel: csrc/cvd_decode_llr.hip. */
+int64_t cvd_viterbi_llr_workspace_bytes(int32_t n, int32_t m, int32_t T, int64_t F);
+int cvd_viterbi_decode_frames_llr(const cvd_code* code, const int8_t* d_soft, int64_t nvals,
+                                  int64_t start, int64_t stride, const int64_t* d_offsets, int64_t F, int32_t T,
+                                  int32_t start_state, int32_t end_state,
+                                  int16_t* d_llr, uint32_t* d_bits, int32_t* d_frames, int64_t* d_stats,
+                                  void* d_work, void* stream);
+
 /* ---- error-exponent engine (alpha_exponent.py, Eq. 7) ---------------------
  * Joint counts of (metric state i, received word r) along received streams
  * (pitch = nseq) for steps t >= burn_in, on a dense (enumerated) model with
