@@ -164,7 +164,9 @@ __device__ __forceinline__ uint64_t mix64(uint64_t x) {
   return x ^ (x >> 31);
 }
 
-__global__ void hash_kernel(const uint32_t* keys, int64_t n, int nw, uint64_t seed, uint64_t* h, uint32_t* v) {
+// hkeep: hash bits kept (all; CVD_LEARN_HASH_BITS narrows them to force collisions in tests)
+__global__ void hash_kernel(const uint32_t* keys, int64_t n, int nw, uint64_t seed, uint64_t hkeep, uint64_t* h,
+                            uint32_t* v) {
   const int64_t t = (int64_t)blockIdx.x * kLB + threadIdx.x;
   if (t >= n) return;
   uint64_t x = seed;
@@ -172,7 +174,7 @@ __global__ void hash_kernel(const uint32_t* keys, int64_t n, int nw, uint64_t se
     const uint64_t lo = keys[(size_t)t * nw + w], hi = w + 1 < nw ? keys[(size_t)t * nw + w + 1] : 0u;
     x = mix64(x ^ (lo | (hi << 32)));
   }
-  h[t] = x;
+  h[t] = x & hkeep;
   v[t] = (uint32_t)t;
 }
 
@@ -400,8 +402,13 @@ int cvd::device_learn_sparse(const CodeDesc& dec, int64_t L, int64_t burn, uint6
   LHIP(sc.alloc(reinterpret_cast<uint8_t*&>(tmp), std::max({tmp_sort, tmp_scan1, tmp_scan2})));
   uint64_t hseed = 0x243F6A8885A308D3ull;
   uint32_t h_coll = 1;
+  // test seam (as CVD_BFS_HASH_BITS): the first CVD_LEARN_HASH_WEAK attempts keep only the low
+  // CVD_LEARN_HASH_BITS bits of each hash, so the collision retry runs; unset: all 64 bits
+  const int64_t hbits = env_int("CVD_LEARN_HASH_BITS", 64), hweak = env_int("CVD_LEARN_HASH_WEAK", 1);
+  const uint64_t hnarrow = hbits > 0 && hbits < 64 ? ((uint64_t)1 << hbits) - 1 : ~0ull;
   for (int attempt = 0; h_coll && attempt < 4; ++attempt, hseed = hseed * 0x9E3779B97F4A7C15ull + 1) {
-    hipLaunchKernelGGL(hash_kernel, dim3(grid_of(nt)), dim3(kLB), 0, st, a.states, nt, nw, hseed, h, v);
+    hipLaunchKernelGGL(hash_kernel, dim3(grid_of(nt)), dim3(kLB), 0, st, a.states, nt, nw, hseed,
+                       attempt < hweak ? hnarrow : ~0ull, h, v);
     size_t ts = tmp_sort;
     LHIP(rocprim::radix_sort_pairs(tmp, ts, h, hs, v, vs, (size_t)nt, 0, 64, st));
     LHIP(hipMemsetAsync(isfirst, 0, (size_t)nt * sizeof(uint32_t), st));
