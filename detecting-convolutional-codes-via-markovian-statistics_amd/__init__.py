@@ -21,8 +21,9 @@ from .blind import (  # noqa: F401
     template_mask, mask_template, mask_extent, parity_sweep, find_parity_checks, identify_code, default_z_min,
 )
 from .decode import (PUNCTURE_PATTERNS, decode_capture, decode_capture_punctured, decode_capture_soft,  # noqa: F401
-                     decode_frames, decode_frames_llr, decode_frames_soft, decode_frames_tailbiting,
-                     decode_frames_tailbiting_soft, depuncture_soft, puncture_pattern, punctured_bits,
+                     decode_frames, decode_frames_llr, decode_frames_llr_punctured, decode_frames_soft,
+                     decode_frames_soft_punctured, decode_frames_tailbiting, decode_frames_tailbiting_soft,
+                     decode_frames_tailbiting_soft_punctured, depuncture_soft, puncture_pattern, punctured_bits,
                      soft_from_bits, sync_punctured, sync_punctured_soft)
 from .exponent import (  # noqa: F401
     TransitionTensor, learn_transition_tensor, chernoff_rhos, compute_error_exponent, spectral_radius,

@@ -63,8 +63,10 @@
       the int64 offsets of --frame-offsets (a frame that does not lie inside the capture is
       skipped); --frame-count F frames (default: as many as fit).  --start-state / --end-state:
       the encoder's state before / after a frame, or any; the defaults, 0 and 0, are terminated
-      frames.  Works with --puncture (the pattern restarts in every frame) and --format soft (not
-      both); an error together with --T or --sync.  Writes <save-dir>/decoded.npy (uint8 [F, 4w],
+      frames.  Works with --puncture (the pattern restarts in every frame), with --format soft, and
+      with both (cvd_viterbi_decode_frames_soft_punctured: punctured frames of confidence values,
+      as a receiver produces them; counted is then the kept values that are not 0); an error
+      together with --T or --sync.  Writes <save-dir>/decoded.npy (uint8 [F, 4w],
       w = ceil(T/32): a row per frame, LSB-first) and <save-dir>/decode_frames.csv, a row per
       frame: frame, offset, status (0 decoded, 1 skipped), distance, errors, counted,
       start_state, end_state; prints the totals and p = errors / counted.
@@ -72,7 +74,9 @@
       encoder starts in the state of the frame's own last m bits and no tail bits are sent),
       decoded by the wrap-around Viterbi algorithm (cvd_viterbi_decode_frames_tailbiting and its
       punctured and soft siblings) with at most --laps I laps (1..8, default 4).  An error
-      together with --start-state / --end-state (neither state is known), --T or --sync.  The
+      together with --start-state / --end-state (neither state is known), --T or --sync, and
+      with --format soft --puncture together (decode_frames_tailbiting_soft_punctured and
+      decode_frames_llr_punctured are reachable from Python and C only).  The
       CSV gains the column laps and status reads 0 tail-biting best path, 1 skipped, 2 best
       tail-biting survivor of the last lap, 3 no tail-biting survivor (start_state !=
       end_state); the summary adds the numbers of such frames and the mean laps.
@@ -100,7 +104,7 @@ import sys
 
 from . import (CONFIG_CODES, DEFAULTS, EXAMPLE_CODES, compute_error_exponent, default_template,
                decode_capture, decode_capture_punctured, decode_capture_soft, decode_frames, decode_frames_soft,
-               decode_frames_llr, decode_frames_tailbiting, decode_frames_tailbiting_soft,
+               decode_frames_llr, decode_frames_soft_punctured, decode_frames_tailbiting, decode_frames_tailbiting_soft,
                find_parity_checks,
                learn_transition_tensor, octal_to_taps, parity_experiment, parity_vector_to_equation, parity_vectors,
                puncture_pattern, punctured_bits, run_experiment, scan_capture, sync_punctured, sync_punctured_soft)
@@ -297,8 +301,9 @@ def parse_args(argv=None):
                 ap.error("decode: --frame decodes frames of T steps each; it does not go with --T or --sync")
             if a.frame_offsets is not None and a.frame_stride is not None:
                 ap.error("decode: --frame-offsets and --frame-stride exclude one another")
-            if a.format == "soft" and a.puncture is not None:
-                ap.error("decode: --frame with --format soft does not take --puncture")
+            if a.tail_biting and a.format == "soft" and a.puncture is not None:
+                ap.error("decode: --tail-biting with --format soft does not take --puncture "
+                         "(decode_frames_tailbiting_soft_punctured: Python and C only)")
             if a.tail_biting and a.states_given:
                 ap.error("decode: --tail-biting does not go with --start-state or --end-state: neither state is known")
         if a.laps is not None and not a.tail_biting:
@@ -474,7 +479,9 @@ def cmd_decode_frames(a, n, m, g1):
         kw.update(start_state=a.start_state, end_state=a.end_state)
         hard, soft = decode_frames, decode_frames_llr if a.llr else decode_frames_soft
     try:
-        if a.format == "soft":
+        if a.format == "soft" and a.puncture is not None:    # terminated frames: parse_args saw to it
+            res = decode_frames_soft_punctured(n, m, g1, a.puncture, load_soft_capture(a.input, a.nbits), a.frame, **kw)
+        elif a.format == "soft":
             res = soft(n, m, g1, load_soft_capture(a.input, a.nbits), a.frame, **kw)
         else:
             res = hard(n, m, g1, load_capture(a.input), a.frame, keep=a.puncture, format=a.format, nbits=a.nbits, **kw)

@@ -198,6 +198,27 @@ EXPORTS = {
                                                      ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
                                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                      ctypes.c_void_p, ctypes.c_void_p]),
+    "cvd_viterbi_decode_frames_soft_punctured": (ctypes.c_int, [ctypes.POINTER(cvd_code), ctypes.c_char_p,
+                                                                ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64,
+                                                                ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p,
+                                                                ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
+                                                                ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
+                                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "cvd_viterbi_decode_frames_tailbiting_soft_punctured": (ctypes.c_int, [ctypes.POINTER(cvd_code), ctypes.c_char_p,
+                                                                           ctypes.c_int32, ctypes.c_void_p,
+                                                                           ctypes.c_int64, ctypes.c_int64,
+                                                                           ctypes.c_int64, ctypes.c_void_p,
+                                                                           ctypes.c_int64, ctypes.c_int32,
+                                                                           ctypes.c_int32, ctypes.c_void_p,
+                                                                           ctypes.c_void_p, ctypes.c_void_p,
+                                                                           ctypes.c_void_p, ctypes.c_void_p]),
+    "cvd_viterbi_decode_frames_llr_punctured": (ctypes.c_int, [ctypes.POINTER(cvd_code), ctypes.c_char_p,
+                                                               ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64,
+                                                               ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p,
+                                                               ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
+                                                               ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
+                                                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                               ctypes.c_void_p]),
     "cvd_count_transitions": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
                                              ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
     "cvd_chernoff_build": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,

@@ -24,6 +24,10 @@ namespace vit {
 constexpr int kWave = 64;
 constexpr int kSeg = 1024;                   // steps staged at once (a multiple of 64)
 constexpr int kStageDw = 3 * kSeg / 32 + 4;  // n <= 3: the segment's dwords, alignment slack, funnel word
+// The frame decoders' +inf at a boundary state that is known: even, above every finite metric
+// with room for T steps on top (kInf + 127 * 3 * 65536 < 2^31; two of them and
+// 2 * 127 * 3 * 65536 stay below 2^31 in the soft-output decoder's alpha + beta)
+constexpr int kInf = 1 << 28;
 
 template <int m>
 struct Shape {
@@ -287,6 +291,12 @@ inline int unsupported(const char* who, const char* what) {
 }
 
 inline int64_t round16(int64_t x) { return (x + 15) / 16 * 16; }
+
+// bytes of a frame's decision words (the frame decoders): T rounded up to 64 steps of max(8, 2^m / 8) bytes
+inline int64_t frame_bytes(int m, int64_t T) {
+  const int64_t spl = ((int64_t)1 << m) > kWave ? ((int64_t)1 << m) / kWave : 1;
+  return (T + 63) / 64 * 64 * spl * 8;
+}
 
 // pick(m, n, &fwd, &join): a file's forward and join kernels of a code shape (m in 1..8, n in 2..3)
 using Kern = void (*)(VArgs);

@@ -1,7 +1,7 @@
-// The three lane types of the capture decoder's forward passes, by how y_t is read: Lane (every
+// The lane types of the capture decoder's forward passes, by how y_t is read: Lane (every
 // output bit of a step is in the capture; cvd_decode.hip describes it), PLane (a puncturing
-// pattern says which are; cvd_decode_punct.hip) and SLane (an int8 confidence value per bit;
-// cvd_decode_soft.hip).  Each brings init, run<record>(a, t0, t1, D, dec, st, met) and cand0 /
+// pattern says which are; cvd_decode_punct.hip), SLane (an int8 confidence value per bit;
+// cvd_decode_soft.hip) and PSLane (values behind a pattern; frames only).  Each brings init, run<record>(a, t0, t1, D, dec, st, met) and cand0 /
 // cand1 around cvd_decode_common.h's LaneBase and acs_chunk.  The stream decoders' forward and
 // join kernels and the frame decoder's forward kernels (cvd_decode_frames.hip) are built around
 // them.  Include after <hip/hip_runtime.h>.
@@ -74,13 +74,65 @@ struct Lane : LaneBase<m> {
   }
 };
 
-// pos(t) of include/cvd.h, t in 0..2^31 - 1
-__device__ __forceinline__ int64_t pos_of(const VArgs& a, int64_t t, uint32_t* col) {
+// pos(t) - start of include/cvd.h, t in 0..2^31 - 1
+__device__ __forceinline__ int64_t pos_rel(const VArgs& a, int64_t t, uint32_t* col) {
   const uint32_t tt = (uint32_t)t, per = (uint32_t)a.period;
   const uint32_t r = tt / per, c = tt - r * per;
   *col = c;
   const uint32_t pre = (uint32_t)(a.ppre[c >> 3] >> (8u * (c & 7u))) & 255u;
-  return a.start + (int64_t)r * a.K + pre;
+  return (int64_t)r * a.K + pre;
+}
+
+// pos(t)
+__device__ __forceinline__ int64_t pos_of(const VArgs& a, int64_t t, uint32_t* col) {
+  return a.start + pos_rel(a, t, col);
+}
+
+// Step t of a punctured soft frame whose first value is v[0]: f(j, x) for every output j that the
+// step's column keeps, ascending, x the value in its place.  `a` indexed by the column: in LDS.
+template <class F>
+__device__ __forceinline__ void kept_values(const VArgs& a, const int8_t* v, int64_t t, F f) {
+  uint32_t c;
+  const int8_t* p = v + pos_rel(a, t, &c);
+  const uint32_t keep = (uint32_t)(a.pmask >> (4u * c)) & 7u;    // no bit at or above n
+#pragma unroll
+  for (int j = 0; j < 3; ++j)
+    if ((keep >> j) & 1u) f(j, (int)*p++);
+}
+
+// A soft frame's errors and counted: a lane per step (64 apart) re-encodes the step from the
+// decoded bits -- s_t is the m bits before bit t of row, those before bit 0 are s0 -- and compares
+// the signs of the step's values that are not 0; v: the frame's first value.  punct: the values
+// are those that the pattern of `a` (in LDS) keeps.  Every lane returns the wave's sums.
+template <bool punct>
+__device__ __forceinline__ void count_signs(const VArgs& a, const int8_t* v, const uint32_t* row, uint32_t s0, int T,
+                                            int m, int n, int lane, uint32_t& err, uint32_t& seen) {
+  const uint32_t before = __builtin_bitreverse32(s0);                       // u_{-d} in bit 32 - d
+  err = seen = 0u;
+  for (int t = lane; t < T; t += kWave) {
+    const int w = t >> 5;
+    const uint32_t hi = row[w], lo = w ? row[w - 1] : before;
+    const uint64_t q = ((uint64_t)hi << 32) | lo;
+    const uint32_t sh = (uint32_t)(t & 31);
+    const uint32_t r = (uint32_t)(q >> (sh + 32u - (uint32_t)m)) & ((1u << m) - 1u);   // bit i: u_{t-m+i}
+    const uint32_t ps = __builtin_bitreverse32(r) >> (32 - m);                       // bit d-1: u_{t-d}
+    const uint32_t u = (hi >> sh) & 1u;
+    auto one = [&](int j, int x) {
+      const uint32_t o = (((a.g0 >> j) & u) ^ (uint32_t)__builtin_popcount(a.gs[j] & ps)) & 1u;
+      seen += x != 0;
+      err += x != 0 && (uint32_t)(x > 0) != o;
+    };
+    if constexpr (punct) {
+      kept_values(a, v, t, one);
+    } else {
+      for (int j = 0; j < n; ++j) one(j, v[(int64_t)n * t + j]);
+    }
+  }
+#pragma unroll
+  for (int k = 1; k < kWave; k <<= 1) {
+    err += __shfl_xor(err, k);
+    seen += __shfl_xor(seen, k);
+  }
 }
 
 template <int m, int n>
@@ -270,6 +322,73 @@ struct SLane : LaneBase<m> {
             asum += abs(v);
             vp |= (v & 255) << (8 * j);
           }
+        }
+        acs_chunk<record>(*this, c64, X, cur, met, dec + ((seg - t0) + j0) * SPL,
+                          [&](int jj) { return __builtin_amdgcn_readlane(vp, jj); });
+      }
+    }
+#pragma unroll
+    for (int k = 1; k < kWave; k <<= 1) asum += __shfl_xor(asum, k);
+    return asum;
+  }
+};
+
+// SLane behind a puncturing pattern (the frame decoders' punctured soft calls,
+// cvd_decode_psoft.hip): the candidates, the vectors and the step loop are SLane's; the loader
+// places a step's kept values as PLane places its kept bits, and a byte that the column erases
+// is 0, which is what the contract's v' holds there.
+template <int m, int n>
+struct PSLane : SLane<m, n> {
+  using SLane<m, n>::SPL;
+  using SLane<m, n>::lane;
+
+  // as SLane::run; a: in LDS (indexed by the column).  LDS: st kSoftStageU4 pieces: the kept
+  // values of a segment are at most its n cnt values.
+  template <bool record>
+  __device__ __forceinline__ int run(const VArgs& a, int64_t t0, int64_t t1, int (&X)[SPL], uint64_t* dec, uint4* st,
+                                     int* met) const {
+    int cur = 0;
+    int asum = 0;
+    const int8_t* sb = reinterpret_cast<const int8_t*>(st);
+    const uint32_t per = (uint32_t)a.period, q64 = (uint32_t)kWave / per, r64 = (uint32_t)kWave - q64 * per;
+    for (int64_t seg = t0; seg < t1; seg += kSeg) {
+      const int cnt = (int)min((int64_t)kSeg, t1 - seg);
+      uint32_t c0, c1;
+      const int64_t p0 = pos_of(a, seg, &c0), p1 = pos_of(a, seg + cnt, &c1);   // the segment's values: [p0, p1)
+      const int64_t g0 = p0 >> 4;
+      const int npc = (int)(((p1 + 15) >> 4) - g0);      // <= kSoftStageU4 - 1
+      __syncthreads();                                   // the previous segment has been read
+      for (int i = lane; i < npc; i += kWave) {
+        uint4 v = make_uint4(0u, 0u, 0u, 0u);
+        if (g0 + i < a.nu4) v = a.cap[g0 + i];
+        st[i] = v;
+      }
+      __syncthreads();
+      // lane l: steps seg + l, seg + l + 64, ...: the step's period and column as in PLane::run
+      const uint32_t tt = (uint32_t)seg + (uint32_t)lane;
+      uint32_t rr = tt / per, c = tt - rr * per;
+      const int64_t base = a.start - (g0 << 4);          // pos(t) - base: the value's place in st
+      for (int j0 = 0; j0 < cnt; j0 += kWave) {
+        const int c64 = min(kWave, cnt - j0);
+        int vp = 0;                                      // lane j: the chunk's step j, kept values at their bytes j
+        if (lane < c64) {
+          const uint32_t pre = (uint32_t)(a.ppre[c >> 3] >> (8u * (c & 7u))) & 255u;
+          const uint32_t keep = (uint32_t)(a.pmask >> (4u * c)) & 7u;
+          const int8_t* p = sb + ((uint32_t)(base + (int64_t)rr * a.K) + pre);   // < 16 + 3 kSeg
+#pragma unroll
+          for (int j = 0; j < n; ++j) {
+            if ((keep >> j) & 1u) {
+              const int v = max((int)*p++, -127);
+              asum += abs(v);
+              vp |= (v & 255) << (8 * j);
+            }
+          }
+        }
+        rr += q64;
+        c += r64;
+        if (c >= per) {
+          c -= per;
+          ++rr;
         }
         acs_chunk<record>(*this, c64, X, cur, met, dec + ((seg - t0) + j0) * SPL,
                           [&](int jj) { return __builtin_amdgcn_readlane(vp, jj); });

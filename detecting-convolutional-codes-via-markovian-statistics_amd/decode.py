@@ -26,6 +26,12 @@ is driven back to one by m tail bits) go through cvd_viterbi_decode_frames and i
 and soft siblings (csrc/cvd_decode_frames.hip): decode_frames and decode_frames_soft decode a
 batch of F frames of T steps, at a stride or at given offsets, in one call, with the start and
 end states told to the decoder.
+
+Punctured soft frames (what a receiver produces at the punctured rates) go through
+cvd_viterbi_decode_frames_soft_punctured, _tailbiting_soft_punctured and _llr_punctured
+(csrc/cvd_decode_psoft.hip): decode_frames_soft_punctured, decode_frames_tailbiting_soft_punctured
+and decode_frames_llr_punctured.  The command line reaches the first (decode --frame T --format
+soft --puncture SPEC); the tail-biting and soft-output ones are Python and C only.
 """
 import ctypes
 
@@ -478,17 +484,34 @@ def decode_frames_soft(n, m, gen, soft, T, F=None, start=0, stride=None, offsets
     """cvd_viterbi_decode_frames_soft: decode_frames over a soft capture (int8, as
     decode_capture_soft takes it); start, stride and offsets count values.  distance is the soft
     distance of a frame's path, errors its sign disagreements, counted its non-erased values.
-    Punctured soft frames are not depunctured frame by frame: keep raises NotImplementedError
-    (slice the values to bits and use decode_frames(keep=...))."""
+    Punctured soft frames have a call of their own: keep raises NotImplementedError (use
+    decode_frames_soft_punctured)."""
     if keep is not None:
-        raise NotImplementedError("decode_frames_soft does not depuncture frame by frame: slice the values to hard "
-                                  "bits and use decode_frames(keep=...)")
+        raise NotImplementedError("decode_frames_soft takes no pattern: use decode_frames_soft_punctured")
     dev = device if isinstance(device, torch.device) else _require_gpu(device)
     n, m, T = int(n), int(m), int(T)
     code = as_code(gen, m, 1, n)
     cap, nvals = _soft_buffer(soft, dev)
     return _frames("decode_frames_soft", "cvd_viterbi_decode_frames_soft", (code.c,), (), cap, nvals, n, m, T, n * T, F,
                    start, stride, offsets, start_state, end_state, True, dev)
+
+
+def decode_frames_soft_punctured(n, m, gen, keep, soft, T, F=None, start=0, stride=None, offsets=None, start_state=0,
+                                 end_state=0, device=None):
+    """cvd_viterbi_decode_frames_soft_punctured: decode_frames_soft over punctured frames (802.11a/g
+    PPDUs at rates 2/3 and 3/4 as a demapper leaves them).  keep: anything puncture_pattern takes;
+    the pattern restarts at column 0 in every frame, whose punctured_bits(T, keep) values follow
+    one another from its offset.  The result is decode_frames_soft's on the frames depunctured
+    one by one (zeros where nothing was sent), without that capture ever being built: counted is
+    the number of kept values that are not 0."""
+    dev = device if isinstance(device, torch.device) else _require_gpu(device)
+    n, m, T = int(n), int(m), int(T)
+    code = as_code(gen, m, 1, n)
+    keep = puncture_pattern(keep, n)
+    cap, nvals = _soft_buffer(soft, dev)
+    return _frames("decode_frames_soft_punctured", "cvd_viterbi_decode_frames_soft_punctured",
+                   (code.c, bytes(keep), len(keep)), (), cap, nvals, n, m, T, punctured_bits(max(T, 0), keep), F, start,
+                   stride, offsets, start_state, end_state, True, dev)
 
 
 # ──────────────────────────── tail-biting frames ────────────────────────────
@@ -578,6 +601,22 @@ def decode_frames_tailbiting_soft(n, m, gen, soft, T, F=None, start=0, stride=No
                        nvals, n, m, T, n * T, F, start, stride, offsets, max_laps, True, dev)
 
 
+def decode_frames_tailbiting_soft_punctured(n, m, gen, keep, soft, T, F=None, start=0, stride=None, offsets=None,
+                                            max_laps=None, device=None):
+    """cvd_viterbi_decode_frames_tailbiting_soft_punctured: decode_frames_tailbiting_soft over
+    punctured frames (802.16 FCH and bursts), the pattern `keep` restarting at column 0 in every
+    frame and every lap.  The result is decode_frames_tailbiting_soft's on the frames depunctured
+    one by one.  Python and C only: the command line does not reach it."""
+    dev = device if isinstance(device, torch.device) else _require_gpu(device)
+    n, m, T = int(n), int(m), int(T)
+    code = as_code(gen, m, 1, n)
+    keep = puncture_pattern(keep, n)
+    cap, nvals = _soft_buffer(soft, dev)
+    return _tailbiting("decode_frames_tailbiting_soft_punctured", "cvd_viterbi_decode_frames_tailbiting_soft_punctured",
+                       (code.c, bytes(keep), len(keep)), (), cap, nvals, n, m, T, punctured_bits(max(T, 0), keep), F,
+                       start, stride, offsets, max_laps, True, dev)
+
+
 # ─────────────────────────── soft output per bit ────────────────────────────
 
 LLR_SATURATED = 32767    # include/cvd.h: |L_t| of a step whose other input value has no path
@@ -601,19 +640,43 @@ def decode_frames_llr(n, m, gen, soft, T, F=None, start=0, stride=None, offsets=
     n, m, T = int(n), int(m), int(T)
     code = as_code(gen, m, 1, n)
     cap, nvals = _soft_buffer(soft, dev)
+    return _llr("decode_frames_llr", "cvd_viterbi_decode_frames_llr", (code.c,), cap, nvals, n, m, T, n * T, F, start,
+                stride, offsets, start_state, end_state, dev)
+
+
+def decode_frames_llr_punctured(n, m, gen, keep, soft, T, F=None, start=0, stride=None, offsets=None, start_state=0,
+                                end_state=0, device=None):
+    """cvd_viterbi_decode_frames_llr_punctured: decode_frames_llr over punctured frames, the pattern
+    `keep` (anything puncture_pattern takes) restarting at column 0 in every frame.  The result is
+    decode_frames_llr's on the frames depunctured one by one (zeros where nothing was sent).
+    Python and C only: the command line does not reach it."""
+    dev = device if isinstance(device, torch.device) else _require_gpu(device)
+    n, m, T = int(n), int(m), int(T)
+    code = as_code(gen, m, 1, n)
+    keep = puncture_pattern(keep, n)
+    cap, nvals = _soft_buffer(soft, dev)
+    return _llr("decode_frames_llr_punctured", "cvd_viterbi_decode_frames_llr_punctured",
+                (code.c, bytes(keep), len(keep)), cap, nvals, n, m, T, punctured_bits(max(T, 0), keep), F, start, stride,
+                offsets, start_state, end_state, dev)
+
+
+def _llr(who, entry, lead, cap, nvals, n, m, T, span, F, start, stride, offsets, start_state, end_state, dev):
+    """One call of the library's soft-output decoder `entry`(*lead, soft, nvals, start, stride,
+    offsets, F, T, start_state, end_state, llr, bits, frames, stats, work, stream):
+    decode_frames_llr's dict.  span: the values of a frame."""
     if not 1 <= T <= FRAME_MAX_T:
         raise ValueError(f"T = {T}: a frame has 1..{FRAME_MAX_T} steps")
     ss, es = _frame_state("start_state", start_state, m), _frame_state("end_state", end_state, m)
     if ss >= 0 and es >= 0 and T < m:
         raise ValueError(f"T = {T} < m = {m}: with both states fixed the end state is not reachable")
     w = (T + 31) // 32
-    off, F, start, stride = _frame_placement(nvals, n * T, w, F, start, stride, offsets, dev)
+    off, F, start, stride = _frame_placement(nvals, span, w, F, start, stride, offsets, dev)
     L = _lib.lib()
-    call = L.cvd_viterbi_decode_frames_llr
+    call = getattr(L, entry)
     wbytes = int(L.cvd_viterbi_llr_workspace_bytes(n, m, T, F))
     if wbytes < 0:
         # the decoder itself names an unsupported code shape
-        _lib.check(call(code.c, None, 0, 0, 1, None, 0, T, ss, es, None, None, None, None, None, None))
+        _lib.check(call(*lead, None, 0, 0, 1, None, 0, T, ss, es, None, None, None, None, None, None))
         _lib.check(wbytes)
     with torch.cuda.device(dev):
         llr = torch.empty((F, 32 * w), dtype=torch.int16, device=dev)
@@ -623,11 +686,11 @@ def decode_frames_llr(n, m, gen, soft, T, F=None, start=0, stride=None, offsets=
         if F:
             free = torch.cuda.mem_get_info(dev)[0]
             if wbytes > free:
-                raise MemoryError(f"decode_frames_llr: the workspace of {F} frames of T = {T} steps (m = {m}) is "
+                raise MemoryError(f"{who}: the workspace of {F} frames of T = {T} steps (m = {m}) is "
                                   f"{wbytes} bytes, {free} bytes of device memory are free: decode the frames in pieces")
             stats = torch.zeros(6, dtype=torch.int64, device=dev)
             work = torch.empty(wbytes, dtype=torch.uint8, device=dev) if wbytes else None
-            _lib.check(call(code.c, ctypes.c_void_p(cap.data_ptr()), nvals, start, stride,
+            _lib.check(call(*lead, ctypes.c_void_p(cap.data_ptr()), nvals, start, stride,
                             ctypes.c_void_p(off.data_ptr()) if off is not None else None, F, T, ss, es,
                             ctypes.c_void_p(llr.data_ptr()), ctypes.c_void_p(bits.data_ptr()),
                             ctypes.c_void_p(frames.data_ptr()), ctypes.c_void_p(stats.data_ptr()),

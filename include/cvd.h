@@ -825,6 +825,58 @@ int cvd_viterbi_decode_frames_llr(const cvd_code* code, const int8_t* d_soft, in
                                   int16_t* d_llr, uint32_t* d_bits, int32_t* d_frames, int64_t* d_stats,
                                   void* d_work, void* stream);
 
+/* ---- punctured soft frames: the three frame decoders on values behind a pattern (nothing in the reference) ----
+ * What a receiver hands over at the punctured rates: an 802.11a/g PPDU at rate 2/3 or 3/4 is a
+ * terminated, punctured frame of demapper confidences; 802.16 FCH and bursts are tail-biting,
+ * punctured and soft.  d_soft / nvals are cvd_viterbi_decode_frames_soft's capture, keep / period
+ * cvd_viterbi_decode_punctured's pattern (n in {2, 3}), and the frames are placed as in the frames
+ * contract with span = pos(T) - start.  The three calls are specified bit for bit by one rule:
+ *   For frame f at o_f let, for 0 <= t < T and 0 <= j < n,
+ *     v'_f[n*t + j] = d_soft[pos(t) + rank of j among the kept outputs of keep[t mod period]]
+ *   where keep[t mod period] has bit j, and 0 otherwise, with pos taken with o_f in the place of
+ *   start: exactly cvd_soft_depuncture's definition with start = o_f, so the pattern restarts at
+ *   column 0 in every frame.
+ *   The result of the punctured soft call is the result of the corresponding unpunctured soft
+ *   call (cvd_viterbi_decode_frames_soft, _tailbiting_soft, _llr) on the frames v'_f: every bit,
+ *   every L_t, every field of every record and every total.
+ * Only the placement and the skip test use span = pos(T) - start (stride mode:
+ * start + (F-1)*stride + span <= nvals; offset mode: a frame with o_f < 0 or o_f + span > nvals
+ * is skipped), and the call reads nothing outside [o_f, o_f + span) of a decoded frame, beyond
+ * the readability rule's whole 16-byte pieces below nvals rounded up to 16.  It follows that
+ * counted ([5] of the frames and tail-biting records) is the number of kept values that are not
+ * 0, a kept value of 0 is still an erasure, -128 is still read as -127, the tie rule is
+ * unchanged, and every lap of the tail-biting decoder has step t in column t mod period.
+ * Workspaces: those of the unpunctured soft calls (cvd_viterbi_frames_workspace_bytes with
+ * soft = 1, cvd_viterbi_tailbiting_workspace_bytes with soft = 1, cvd_viterbi_llr_workspace_bytes):
+ * a decision word or a checkpoint does not depend on the pattern.  The environment variables of
+ * those calls apply.
+ * CVD_E_INVALID (CVD_E_UNSUPPORTED for the code shape), before the device is touched,
+ * cvd_last_error() naming viterbi_decode_frames_soft_punctured,
+ * viterbi_decode_frames_tailbiting_soft_punctured or viterbi_decode_frames_llr_punctured: every
+ * case of the unpunctured soft sibling, and a bad pattern (null keep, period outside 1..16, a
+ * zero column, a bit at or above n) as cvd_viterbi_decode_punctured reports it; an int64
+ * overflow on the way to span.  F == 0: CVD_OK without a launch.  Asynchronous on `stream`.
+ * Kernels: csrc/cvd_decode_psoft.hip (the lane type PSLane of csrc/cvd_decode_lanes.h around
+ * the bodies that the unpunctured decoders' kernels are built from). */
+int cvd_viterbi_decode_frames_soft_punctured(const cvd_code* code, const uint8_t* keep, int32_t period,
+                                             const int8_t* d_soft, int64_t nvals,
+                                             int64_t start, int64_t stride, const int64_t* d_offsets, int64_t F,
+                                             int32_t T, int32_t start_state, int32_t end_state,
+                                             uint32_t* d_bits, int32_t* d_frames, int64_t* d_stats, void* d_work,
+                                             void* stream);
+int cvd_viterbi_decode_frames_tailbiting_soft_punctured(const cvd_code* code, const uint8_t* keep, int32_t period,
+                                                        const int8_t* d_soft, int64_t nvals,
+                                                        int64_t start, int64_t stride, const int64_t* d_offsets,
+                                                        int64_t F, int32_t T, int32_t max_laps,
+                                                        uint32_t* d_bits, int32_t* d_frames, int64_t* d_stats,
+                                                        void* d_work, void* stream);
+int cvd_viterbi_decode_frames_llr_punctured(const cvd_code* code, const uint8_t* keep, int32_t period,
+                                            const int8_t* d_soft, int64_t nvals,
+                                            int64_t start, int64_t stride, const int64_t* d_offsets, int64_t F,
+                                            int32_t T, int32_t start_state, int32_t end_state,
+                                            int16_t* d_llr, uint32_t* d_bits, int32_t* d_frames, int64_t* d_stats,
+                                            void* d_work, void* stream);
+
 /* ---- error-exponent engine (alpha_exponent.py, Eq. 7) ---------------------
  * Joint counts of (metric state i, received word r) along received streams
  * (pitch = nseq) for steps t >= burn_in, on a dense (enumerated) model with
