@@ -37,6 +37,7 @@
              [--out-bits FILE.npy] [--puncture SPEC [--sync T0]]
              [--frame T [--frame-count F] [--frame-stride B | --frame-offsets FILE.npy]
               [--start-state S|any] [--end-state S|any] | [--tail-biting [--laps I]]] [--llr]
+             [--list L [--crc SPEC [--crc-first A] [--crc-count C] [--crc-expect X]]]
       (nothing in the reference) -- what was sent: the hard-decision Viterbi decoder of the
       k = 1 code C over the capture from bit S (cvd_viterbi_decode: the Eq. 4-5 recursion with
       its survivor decisions kept, exact whatever the block split); writes the decoded bits to
@@ -87,6 +88,20 @@
       tail of a terminated frame).  The CSV's columns are then frame, offset, status, distance,
       zeros (undecided bits), weakest (the smallest |value| of the frame), saturated, end_state.
       An error without --frame, without --format soft, with --tail-biting or with --puncture.
+      --frame T --format soft --list L: list decoding (cvd_viterbi_decode_frames_list): the L best
+      paths of every frame, 1 <= L <= 8, T <= 8192.  decoded.npy is then uint8 [F, L, 4w] and the CSV
+      has a row per (frame, path): frame, path, offset, status, distance, start_state, end_state
+      (distance and the states -1 where a frame has fewer than L paths).  With --crc SPEC (crc8-lte,
+      crc16-ccitt, crc24a, crc24b, crc32, or WIDTH:POLY[:INIT[:EXPECT]] with the width decimal and the
+      others hexadecimal) every path's bits are checked on the device (cvd_frames_crc) over --crc-count
+      C bits from bit --crc-first A (defaults: 0, and everything before the CRC and the m tail bits
+      of a fixed end state), the bits in the order decoded, the CRC's first bit most significant, and
+      the first path of a frame whose value is --crc-expect X (hexadecimal; default: the spec's) is
+      chosen: decoded.npy is the chosen rows [F, 4w] (path 0 where none passes) and the CSV has a row
+      per frame: frame, offset, status, paths, choice (-1: none), crc_ok, distance (of the chosen
+      path), distance0, start_state, end_state; the summary prints decoded, ok and rescued (frames
+      whose path 0 fails and a later one passes).  An error without --frame, without --format soft,
+      with --tail-biting, --puncture, --llr, --T or --sync, and --crc* without --list.
 
 Codes: the BASELINE configurations (m2, m6, r23_m4), the demo presets (example:1,
 example:2, demo_script.py:35-52), or oct:G0,G1[,G2] -- k = 1 generators in octal (MSB =
@@ -105,6 +120,7 @@ import sys
 from . import (CONFIG_CODES, DEFAULTS, EXAMPLE_CODES, compute_error_exponent, default_template,
                decode_capture, decode_capture_punctured, decode_capture_soft, decode_frames, decode_frames_soft,
                decode_frames_llr, decode_frames_soft_punctured, decode_frames_tailbiting, decode_frames_tailbiting_soft,
+               crc_spec, decode_frames_crc, decode_frames_list,
                find_parity_checks,
                learn_transition_tensor, octal_to_taps, parity_experiment, parity_vector_to_equation, parity_vectors,
                puncture_pattern, punctured_bits, run_experiment, scan_capture, sync_punctured, sync_punctured_soft)
@@ -255,6 +271,18 @@ def parser():
                    help="with --frame and --format soft: also write llr.npy, a max-log-MAP value per bit "
                         "(not with --tail-biting or --puncture)")
     d.add_argument("--out-llr", default=None, help="with --llr: the .npy of values (default <save-dir>/llr.npy)")
+    d.add_argument("--list", type=int, default=None, metavar="L",
+                   help="with --frame and --format soft: the L best paths of every frame (1..8; not with "
+                        "--tail-biting, --puncture or --llr)")
+    d.add_argument("--crc", default=None, metavar="SPEC",
+                   help="with --list: choose of every frame the first path that passes this CRC (crc8-lte, "
+                        "crc16-ccitt, crc24a, crc24b, crc32 or WIDTH:POLY[:INIT[:EXPECT]], the width decimal, "
+                        "the others hexadecimal)")
+    d.add_argument("--crc-first", type=int, default=None, metavar="A", help="with --crc: the first bit under the CRC (default 0)")
+    d.add_argument("--crc-count", type=int, default=None, metavar="C",
+                   help="with --crc: the bits under the CRC (default: all before the CRC and a fixed end state's tail)")
+    d.add_argument("--crc-expect", type=lambda t: int(t, 16), default=None, metavar="X",
+                   help="with --crc: the value (hexadecimal) of a frame that passes (default: the spec's)")
     d.set_defaults(states_given=False)
 
     c = sub.add_parser("compare", help="P_err figures of both detectors (plots_compare.py)")
@@ -319,6 +347,24 @@ def parse_args(argv=None):
                 ap.error("decode: --llr does not take --puncture")
         elif a.out_llr is not None:
             ap.error("decode: --out-llr needs --llr")
+        if a.list is not None:
+            if a.frame is None:
+                ap.error("decode: --list needs --frame")
+            if a.format != "soft":
+                ap.error("decode: --list needs --format soft")
+            if a.tail_biting or a.puncture is not None or a.llr:
+                ap.error("decode: --list does not go with --tail-biting, --puncture or --llr")
+            if not 1 <= a.list <= 8:
+                ap.error("decode: --list takes 1..8 paths")
+            if a.crc is not None:
+                try:
+                    crc_spec(a.crc)
+                except ValueError as e:
+                    ap.error(f"decode: {e}")
+        if a.crc is None and (a.crc_first is not None or a.crc_count is not None or a.crc_expect is not None):
+            ap.error("decode: --crc-first, --crc-count and --crc-expect need --crc")
+        if a.crc is not None and a.list is None:
+            ap.error("decode: --crc needs --list")
     return a
 
 
@@ -460,6 +506,59 @@ DECODE_COLUMNS = ["T", "errors", "ber", "start_state", "end_state", "blocks", "f
 FRAME_COLUMNS = ["frame", "offset", "status", "distance", "errors", "counted", "start_state", "end_state"]
 TAILBITING_COLUMNS = FRAME_COLUMNS + ["laps"]
 LLR_COLUMNS = ["frame", "offset", "status", "distance", "zeros", "weakest", "saturated", "end_state"]
+LIST_COLUMNS = ["frame", "path", "offset", "status", "distance", "start_state", "end_state"]
+CRC_COLUMNS = ["frame", "offset", "status", "paths", "choice", "crc_ok", "distance", "distance0", "start_state",
+               "end_state"]
+
+
+def cmd_decode_list(a, n, m, g1, offsets):
+    """decode --frame --list: the rows of bits and a CSV row per (frame, path), or with --crc the
+    chosen rows and a CSV row per frame."""
+    import numpy as np
+    kw = dict(F=a.frame_count, start=a.start, stride=a.frame_stride, offsets=offsets, start_state=a.start_state,
+              end_state=a.end_state)
+    soft = load_soft_capture(a.input, a.nbits)
+    try:
+        if a.crc is None:
+            res = decode_frames_list(n, m, g1, soft, a.frame, a.list, **kw)
+        else:
+            res = decode_frames_crc(n, m, g1, soft, a.frame, a.list, a.crc, first=a.crc_first or 0, count=a.crc_count,
+                                    expect=a.crc_expect, **kw)
+    except ValueError as e:
+        raise SystemExit(f"decode: {e}")
+    if offsets is None:
+        stride = a.frame_stride if a.frame_stride is not None else n * a.frame
+        offsets = a.start + stride * np.arange(res["F"], dtype=np.int64)
+    out = a.out or os.path.join(a.save_dir, "decode_frames.csv")
+    out_bits = a.out_bits or os.path.join(a.save_dir, "decoded.npy")
+    for path in (out, out_bits):
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    bits = (res["bits"] if a.crc is None else res["chosen_bits"]).cpu().numpy()
+    with open(out_bits, "wb") as f:             # (np.save would append .npy to another suffix)
+        np.save(f, bits)
+    dist, s0, sT = (res[k].cpu().numpy() for k in ("distance", "start_states", "end_states"))
+    status, paths = res["status"].cpu().numpy(), res["paths"].cpu().numpy()
+    with open(out, "w", newline="") as f:
+        wr = csv.writer(f)
+        if a.crc is None:
+            wr.writerow(LIST_COLUMNS)
+            for i in range(res["F"]):
+                for l in range(res["L"]):
+                    wr.writerow([i, l, int(offsets[i]), int(status[i]), int(dist[i, l]), int(s0[i, l]), int(sT[i, l])])
+        else:
+            wr.writerow(CRC_COLUMNS)
+            choice, ok = res["choice"].cpu().numpy(), res["crc_ok"].cpu().numpy()
+            for i in range(res["F"]):
+                c = max(int(choice[i]), 0)
+                wr.writerow([i, int(offsets[i]), int(status[i]), int(paths[i]), int(choice[i]), int(ok[i]),
+                             int(dist[i, c]), int(dist[i, 0]), int(s0[i, c]), int(sT[i, c])])
+    print(f"Decoded {res['decoded']} frames of {res['T']} steps ({res['skipped']} skipped): {res['total_paths']} paths "
+          f"in lists of {res['L']}, distance of the best paths {res['total_distance']}")
+    if a.crc is not None:
+        print(f"CRC {a.crc}: {res['decoded']} decoded, {res['ok']} ok, {res['rescued']} rescued by a path behind the best")
+    print("Saved bits to", out_bits, "(" + " x ".join(str(d) for d in bits.shape) + " bytes)")
+    print("Saved results to", out)
+    return 0
 
 
 def cmd_decode_frames(a, n, m, g1):
@@ -471,6 +570,8 @@ def cmd_decode_frames(a, n, m, g1):
         if offsets.dtype != np.int64:
             raise SystemExit(f"{a.frame_offsets}: frame offsets are int64, not {offsets.dtype}")
         offsets = offsets.reshape(-1)
+    if a.list is not None:
+        return cmd_decode_list(a, n, m, g1, offsets)
     kw = dict(F=a.frame_count, start=a.start, stride=a.frame_stride, offsets=offsets)
     if a.tail_biting:
         kw["max_laps"] = a.laps

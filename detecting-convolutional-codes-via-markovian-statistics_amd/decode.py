@@ -32,6 +32,10 @@ cvd_viterbi_decode_frames_soft_punctured, _tailbiting_soft_punctured and _llr_pu
 (csrc/cvd_decode_psoft.hip): decode_frames_soft_punctured, decode_frames_tailbiting_soft_punctured
 and decode_frames_llr_punctured.  The command line reaches the first (decode --frame T --format
 soft --puncture SPEC); the tail-biting and soft-output ones are Python and C only.
+
+List decoding (cvd_viterbi_decode_frames_list, csrc/cvd_decode_list.hip): decode_frames_list returns
+the L best paths of every soft frame, frames_crc (cvd_frames_crc) checks rows of decoded bits against
+a CRC on the device, and decode_frames_crc picks of every frame the first path that passes.
 """
 import ctypes
 
@@ -700,3 +704,180 @@ def _llr(who, entry, lead, cap, nvals, n, m, T, span, F, start, stride, offsets,
             "end_states": frames[:, 2], "status": frames[:, 3], "weakest": frames[:, 4], "saturated": frames[:, 5],
             "T": T, "F": F, "decoded": int(s[1]), "skipped": int(s[2]), "total_distance": int(s[0]),
             "total_zeros": int(s[3]), "total_saturated": int(s[4]), "words": int(s[5])}
+
+
+# ───────────────────────── list decoding and the CRC ────────────────────────
+
+LIST_MAX_L = 8           # include/cvd.h CVD_VITERBI_LIST_MAX_L
+LIST_MAX_T = 8192        # include/cvd.h CVD_VITERBI_LIST_MAX_T
+
+CRC_SPECS = {            # name: (width, poly, init, expect)
+    "crc8-lte": (8, 0x9B, 0, 0),
+    "crc16-ccitt": (16, 0x1021, 0, 0),
+    "crc24a": (24, 0x864CFB, 0, 0),
+    "crc24b": (24, 0x800063, 0, 0),
+    "crc32": (32, 0x04C11DB7, 0xFFFFFFFF, 0xFFFFFFFF),
+}
+
+
+def crc_spec(spec):
+    """(width, poly, init, expect) of a name in CRC_SPECS, of "WIDTH:POLY[:INIT[:EXPECT]]" (the
+    width decimal, the others hexadecimal; init and expect default to 0), or of such a tuple.
+    width is 1..32 and the others are below 2^width."""
+    if isinstance(spec, str):
+        if spec in CRC_SPECS:
+            return CRC_SPECS[spec]
+        parts = spec.split(":")
+        try:
+            if not 2 <= len(parts) <= 4:
+                raise ValueError
+            vals = [int(parts[0], 10)] + [int(p, 16) for p in parts[1:]]
+        except ValueError:
+            raise ValueError(f"CRC {spec!r}: WIDTH:POLY[:INIT[:EXPECT]] with the width decimal and the others "
+                             f"hexadecimal, or one of {sorted(CRC_SPECS)}") from None
+        vals += [0] * (4 - len(vals))
+    else:
+        vals = [int(v) for v in spec]
+        if len(vals) != 4:
+            raise ValueError("a CRC is (width, poly, init, expect)")
+    width, poly, init, expect = vals
+    if not 1 <= width <= 32:
+        raise ValueError(f"CRC {spec!r}: the width must be 1..32")
+    if any(v < 0 or v >> width for v in (poly, init, expect)):
+        raise ValueError(f"CRC {spec!r}: poly, init and expect must be below 2^{width}")
+    return width, poly, init, expect
+
+
+def _list_call(who, code, cap, nvals, n, m, T, L, F, start, stride, offsets, start_state, end_state, dev):
+    """One call of cvd_viterbi_decode_frames_list: (bits [F, L, 4w], paths [F, L, 3], frames [F, 2],
+    the five stats, F)."""
+    if not 1 <= T <= LIST_MAX_T:
+        raise ValueError(f"T = {T}: a frame of the list decoder has 1..{LIST_MAX_T} steps")
+    if not 1 <= L <= LIST_MAX_L:
+        raise ValueError(f"L = {L}: the list holds 1..{LIST_MAX_L} paths")
+    ss, es = _frame_state("start_state", start_state, m), _frame_state("end_state", end_state, m)
+    if ss >= 0 and es >= 0 and T < m:
+        raise ValueError(f"T = {T} < m = {m}: with both states fixed the end state is not reachable")
+    w = (T + 31) // 32
+    off, F, start, stride = _frame_placement(nvals, n * T, L * w, F, start, stride, offsets, dev)
+    lib = _lib.lib()
+    call = lib.cvd_viterbi_decode_frames_list
+    wbytes = int(lib.cvd_viterbi_list_workspace_bytes(n, m, T, F, L))
+    if wbytes < 0:
+        # the decoder itself names an unsupported code shape
+        _lib.check(call(code.c, None, 0, 0, 1, None, 0, T, ss, es, L, None, None, None, None, None, None))
+        _lib.check(wbytes)
+    with torch.cuda.device(dev):
+        bits = torch.empty((F, L, 4 * w), dtype=torch.uint8, device=dev)
+        paths = torch.empty((F, L, 3), dtype=torch.int32, device=dev)
+        frames = torch.empty((F, 2), dtype=torch.int32, device=dev)
+        s = [0, 0, 0, 0, w]
+        if F:
+            free = torch.cuda.mem_get_info(dev)[0]
+            if wbytes > free:
+                raise MemoryError(f"{who}: the workspace of {F} frames of T = {T} steps (m = {m}, L = {L}) is "
+                                  f"{wbytes} bytes, {free} bytes of device memory are free: decode the frames in pieces")
+            stats = torch.zeros(5, dtype=torch.int64, device=dev)
+            work = torch.empty(wbytes, dtype=torch.uint8, device=dev) if wbytes else None
+            _lib.check(call(code.c, ctypes.c_void_p(cap.data_ptr()), nvals, start, stride,
+                            ctypes.c_void_p(off.data_ptr()) if off is not None else None, F, T, ss, es, L,
+                            ctypes.c_void_p(bits.data_ptr()), ctypes.c_void_p(paths.data_ptr()),
+                            ctypes.c_void_p(frames.data_ptr()), ctypes.c_void_p(stats.data_ptr()),
+                            ctypes.c_void_p(work.data_ptr()) if work is not None else None, _stream_ptr()))
+            s = stats.cpu().tolist()     # synchronises: cap, off and work may be freed on return
+    return bits, paths, frames, s, F
+
+
+def decode_frames_list(n, m, gen, soft, T, L, F=None, start=0, stride=None, offsets=None, start_state=0, end_state=0,
+                       device=None):
+    """cvd_viterbi_decode_frames_list: decode_frames_soft returning the L best paths of every frame
+    (the parallel list Viterbi algorithm), 1 <= L <= 8, 1 <= T <= 8192.  The frames of the soft
+    capture `soft` (int8) are placed as decode_frames places them; start, stride and offsets count
+    values.  Path 0 is decode_frames_soft's; distances do not decrease along the list.
+    Returns a dict: bits (device uint8 [F, L, 4w], w = ceil(T/32): row (f, l) is path l of frame f,
+    LSB-packed, zero where the path is absent), distance, start_states, end_states (device int32
+    [F, L]; -1 where absent), paths (device int32 [F]: how many were found) and status (0 decoded,
+    1 skipped); total_distance (of the paths 0), decoded, skipped, total_paths, words (w), T, F, L."""
+    dev = device if isinstance(device, torch.device) else _require_gpu(device)
+    n, m, T, L = int(n), int(m), int(T), int(L)
+    code = as_code(gen, m, 1, n)
+    cap, nvals = _soft_buffer(soft, dev)
+    bits, paths, frames, s, F = _list_call("decode_frames_list", code, cap, nvals, n, m, T, L, F, start, stride, offsets,
+                                           start_state, end_state, dev)
+    return {"bits": bits, "distance": paths[:, :, 0], "start_states": paths[:, :, 1], "end_states": paths[:, :, 2],
+            "paths": frames[:, 0], "status": frames[:, 1], "total_distance": int(s[0]), "decoded": int(s[1]),
+            "skipped": int(s[2]), "total_paths": int(s[3]), "words": int(s[4]), "T": T, "F": F, "L": L}
+
+
+def frames_crc(bits, first, count, spec, device=None):
+    """cvd_frames_crc over rows of decoded bits: `bits` is uint8 [..., 4w] (a device tensor or a
+    numpy array; any layout that the frame decoders write: bit t of a row is bit t & 7 of byte
+    t >> 3), the CRC `spec` (anything crc_spec takes) runs over the `count` bits from bit `first` of
+    every row and is compared with the width bits that follow, the first of them most significant.
+    Returns the values register ^ field as an int64 tensor in 0..2^32 - 1 of the leading shape: 0
+    where an appended CRC matches (crc_spec's `expect` in general)."""
+    width, poly, init, _ = crc_spec(spec)
+    first, count = int(first), int(count)
+    if isinstance(bits, np.ndarray):
+        bits = torch.from_numpy(np.ascontiguousarray(bits))
+    if not isinstance(bits, torch.Tensor) or bits.dtype != torch.uint8 or bits.dim() < 1 or bits.shape[-1] % 4 \
+            or bits.shape[-1] == 0:
+        raise TypeError("rows of bits are a numpy array or torch tensor of uint8 [..., 4w]")
+    if first < 0 or count < 0 or first + count + width > 8 * bits.shape[-1]:
+        raise ValueError(f"first = {first}, count = {count}: the data and the {width} bits behind them must lie "
+                         f"inside the {8 * bits.shape[-1]} bits of a row")
+    if bits.is_cuda and device is None:
+        dev = bits.device
+    else:
+        dev = device if isinstance(device, torch.device) else _require_gpu(device)
+    lead, w = bits.shape[:-1], bits.shape[-1] // 4
+    rows = int(np.prod(lead, dtype=np.int64))
+    with torch.cuda.device(dev):
+        buf = bits.to(dev).contiguous()
+        if buf.data_ptr() % 4:
+            buf = buf.clone()
+        value = torch.zeros(max(rows, 1), dtype=torch.int32, device=dev)
+        _lib.check(_lib.lib().cvd_frames_crc(ctypes.c_void_p(buf.data_ptr()) if rows else None, rows, w, first, count,
+                                             width, poly, init, ctypes.c_void_p(value.data_ptr()), _stream_ptr()))
+        out = (value[:rows].to(torch.int64) & 0xFFFFFFFF).reshape(lead)
+        torch.cuda.current_stream().synchronize()        # buf may be freed on return
+    return out
+
+
+def decode_frames_crc(n, m, gen, soft, T, L, crc, first=0, count=None, expect=None, F=None, start=0, stride=None,
+                      offsets=None, start_state=0, end_state=0, device=None):
+    """decode_frames_list and the CRC `crc` (anything crc_spec takes) over all F L rows on the
+    device: of every frame the first path of the list that passes the check.  The CRC runs over
+    `count` bits from bit `first` (count=None: T - first - width - (m if end_state is fixed else 0), a frame
+    of data || CRC || tail) and a path passes when its value equals `expect` (None: the spec's).
+    Returns decode_frames_list's dict and: value (device int64 [F, L]), choice (device int32 [F]: the
+    lowest present l whose value equals expect, -1 if none), crc_ok (device bool [F]), chosen_bits
+    (device uint8 [F, 4w]: the chosen row, path 0 where none passes), chosen_distance (device int32
+    [F]), and the totals ok (frames with crc_ok) and rescued (frames with choice > 0)."""
+    dev = device if isinstance(device, torch.device) else _require_gpu(device)
+    n, m, T, L = int(n), int(m), int(T), int(L)
+    width, poly, init, exp0 = crc_spec(crc)
+    expect = exp0 if expect is None else int(expect)
+    if expect < 0 or expect >> width:
+        raise ValueError(f"expect = {expect}: a value below 2^{width}")
+    first = int(first)
+    if count is None:
+        count = T - width - first - (m if end_state is not None else 0)
+    count = int(count)
+    if first < 0 or count < 0 or first + count + width > T:
+        raise ValueError(f"first = {first}, count = {count}: the data and the {width} CRC bits must lie inside the "
+                         f"{T} bits of a frame")
+    res = decode_frames_list(n, m, gen, soft, T, L, F=F, start=start, stride=stride, offsets=offsets,
+                             start_state=start_state, end_state=end_state, device=dev)
+    F = res["F"]
+    with torch.cuda.device(dev):
+        value = frames_crc(res["bits"], first, count, (width, poly, init, expect), device=dev)
+        present = torch.arange(L, device=dev)[None, :] < res["paths"][:, None]
+        hit = (value == expect) & present
+        ok = hit.any(dim=1)
+        choice = torch.where(ok, hit.to(torch.int32).argmax(dim=1), torch.full_like(res["paths"], -1, dtype=torch.int64))
+        pick = choice.clamp(min=0)
+        rows = torch.arange(F, device=dev)
+        res.update(value=value, choice=choice.to(torch.int32), crc_ok=ok, chosen_bits=res["bits"][rows, pick],
+                   chosen_distance=res["distance"][rows, pick], ok=int(ok.sum()), rescued=int((choice > 0).sum()))
+    return res

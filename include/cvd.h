@@ -877,6 +877,95 @@ int cvd_viterbi_decode_frames_llr_punctured(const cvd_code* code, const uint8_t*
                                             int16_t* d_llr, uint32_t* d_bits, int32_t* d_frames, int64_t* d_stats,
                                             void* d_work, void* stream);
 
+/* ---- list decoding of soft frames, and a CRC over rows of decoded bits (nothing in the reference) ----
+ * Every frame decoder above ends in one row of bits per frame and cannot say whether it is right.
+ * The frames they were built for carry the answer: an 802.11 PPDU ends in an FCS, GSM / EDGE and
+ * LTE control blocks carry a CRC, AX.25 and CCSDS packets a CRC-16.  cvd_viterbi_decode_frames_list
+ * returns the L best paths of every frame (the parallel list Viterbi algorithm) and cvd_frames_crc
+ * checks rows of bits on the device, so that the first candidate that passes is picked without
+ * the bits leaving the GPU: the usual 1 to 2 dB of frame error rate on short frames.
+ * Inherited unchanged from cvd_viterbi_decode_frames_soft: the code shapes (k = 1, n in {2, 3},
+ * 1 <= m <= 8, else CVD_E_UNSUPPORTED), the int8 capture (-128 read as -127, 0 an erasure, 16-byte
+ * alignment and readability) and cost(out, t), states and branches, the placement of the frames
+ * (stride mode, or d_offsets with skipped frames; span = n*T), CVD_FRAME_ANY and the rule T >= m
+ * when both states are fixed, and F == 0 (CVD_OK, no launch, nothing written).  Here
+ * 1 <= T <= CVD_VITERBI_LIST_MAX_T and 1 <= L <= CVD_VITERBI_LIST_MAX_L: a frame's decisions cost
+ * 2^m * L / 2 bytes per step, 8 MiB per wave at the caps with m = 8; list decoding pays on short
+ * frames.
+ * The recursion of one frame, over the integers, unnormalised; a list holds at most L values in
+ * ascending order and "absent" stands in the place of +inf (a sequential decoder written from this
+ * text reproduces every output bit for bit).  ps_b = (s' >> 1) | (b << (m-1)) and out as in
+ * cvd_viterbi_decode:
+ *   A_0(s) = [0] for every s if start_state is CVD_FRAME_ANY, else for s = start_state only; every
+ *   other list is empty.
+ *   For step t and next state s', u = s' & 1: the candidates are
+ *     c(b, r) = A_t(ps_b)[r] + cost(out(ps_b, u), t)   for b in {0, 1} and every present rank r;
+ *   A_{t+1}(s') is the first min(L, number of candidates) of them in ascending order of the triple
+ *   (c, b, r), and dec_t(s')[rank] = (b, r) of the candidate that took that rank.
+ *   End: with end_state = e the end list is (A_T(e)[r], e, r) in the order of r; with
+ *   CVD_FRAME_ANY it is the first L of all present (A_T(s)[r], s, r) in ascending order of that
+ *   triple.  P, the number of paths found, is its length.
+ *   Path l, 0 <= l < P, starts from the l-th end entry (distance, s_T, r_T).  For t = T-1 .. 0:
+ *     u_t = s_{t+1} & 1;  (b, r) = dec_t(s_{t+1})[r_{t+1}];  s_t = (s_{t+1} >> 1) | (b << (m-1));  r_t = r.
+ * Consequences (checked on a sequential decoder of this text): path 0 is
+ * cvd_viterbi_decode_frames_soft's, in bits, distance, s_0 and s_T (the order (c, b, r) reduces
+ * to `val < best`, ties keep b = 0, and the end rule to the lowest-index state of minimal D_T);
+ * the result for L is the first L paths of the result for any L' > L; distances are non-decreasing
+ * in l; with a fixed start state the rows of a frame are pairwise distinct, with CVD_FRAME_ANY the
+ * pairs (s_0, row) are; with both states fixed P = min(L, 2^(T-m)); for a fixed start state the
+ * distances are the L smallest costs over all inputs that satisfy the end condition.
+ * d_bits: F*L rows of w = ceil(T/32) words; row f*L + l holds path l of frame f, bit t = u_t LSB
+ * first, padding bits zero; the row of an absent path (l >= P) is zero.
+ * d_paths: int32[F][L][3], 4-byte aligned: {distance, s_0 as traced, s_T}; an absent path is
+ * {-1, -1, -1}.
+ * d_frames: int32[F][2], 4-byte aligned: {P in 0..L, status: 0 decoded, 1 skipped}.  A skipped
+ * frame (offset mode: o_f < 0 or o_f + span > nvals) has zero rows, absent paths and {0, 1}, and
+ * nothing is read for it.
+ * d_stats: int64[5], written (not accumulated), 8-byte aligned:
+ *   [0] sum of the path-0 distances  [1] frames decoded  [2] frames skipped  [3] sum of P  [4] w
+ * All sums are integer sums, so the result does not depend on the launch shape.
+ * CVD_E_INVALID, before the device is touched, cvd_last_error() naming viterbi_decode_frames_list,
+ * for: every case that cvd_viterbi_decode_frames_soft lists; L outside 1..8; and when F > 0: T
+ * outside 1..8192; F*L*w >= 2^31 words; a null or misaligned d_paths or d_frames (4-byte).
+ * d_work: cvd_viterbi_list_workspace_bytes(n, m, T, F, L) bytes, 16-byte aligned.  The kernel keeps
+ * a tile of decisions in LDS: tsteps = min(T, 16384 / (2^m * LL / 2)) steps, LL = 2, 4 or 8 the
+ * least of them that is >= L.  A frame of at most tsteps steps needs no workspace: 0, and a null
+ * d_work is allowed.  Otherwise ceil(T / tsteps) - 1 tiles (tsteps * 2^m * LL / 2 bytes each,
+ * rounded up to 16) per wave of the launch (at most 8,192 waves, as many as the frames, and as
+ * many as about 1 GiB holds): per wave, not per frame, a wave reuses its slice.  The environment
+ * variables CVD_LIST_WAVES (the wave cap) and CVD_LIST_LDS_BYTES (the tile's bytes in the place of
+ * 16384, clamped to 1024..49152), read at both calls, are for tests and measurements.  0 at
+ * F == 0; < 0 with the error set for n, m outside the shapes, L outside 1..8, T outside 1..8192 or
+ * F < 0.  Asynchronous on `stream`: one launch.  Kernels: csrc/cvd_decode_list.hip. */
+#define CVD_VITERBI_LIST_MAX_L 8
+#define CVD_VITERBI_LIST_MAX_T 8192
+int64_t cvd_viterbi_list_workspace_bytes(int32_t n, int32_t m, int32_t T, int64_t F, int32_t L);
+int cvd_viterbi_decode_frames_list(const cvd_code* code, const int8_t* d_soft, int64_t nvals,
+                                   int64_t start, int64_t stride, const int64_t* d_offsets, int64_t F, int32_t T,
+                                   int32_t start_state, int32_t end_state, int32_t L,
+                                   uint32_t* d_bits, int32_t* d_paths, int32_t* d_frames, int64_t* d_stats,
+                                   void* d_work, void* stream);
+/* A CRC over rows of bits in any layout that the decoders write (cvd_viterbi_decode_frames*, the
+ * tail-biting calls, the list): `rows` rows of w words, bit t of a row = bit (t & 31) of word
+ * t >> 5, called u_t.  One 32-bit value per row.  With mask = 2^width - 1:
+ *   reg = init & mask;
+ *   for i = 0 .. count-1:  fb = (bit width-1 of reg) ^ u_{first+i};  reg = (reg << 1) & mask;
+ *                          if fb, reg ^= poly;
+ *   field = sum over i < width of u_{first+count+i} << (width-1-i): the width bits that follow the
+ *   data, the first of them most significant;
+ *   d_value[row] = reg ^ field.
+ * So 0 says "the appended CRC matches"; a CRC masked with an identity (an LTE DCI's RNTI) yields
+ * the identity; an 802.11 FCS (the complemented CRC-32, init all ones, the bits in transmission
+ * order) yields 0xFFFFFFFF.  Reflected CRCs are served by feeding the bits in transmission order;
+ * there is no reflection parameter.
+ * CVD_E_INVALID, before the device is touched, cvd_last_error() naming frames_crc, for: width
+ * outside 1..32; poly or init with bits at or above width; first < 0 or count < 0; w < 1 or
+ * rows < 0; first + count + width > 32*w; a null or misaligned (4-byte) d_bits or d_value when
+ * rows > 0.  rows == 0: CVD_OK, nothing written.  d_value: `rows` uint32.  Asynchronous on
+ * `stream`.  Kernel: csrc/cvd_decode_list.hip. */
+int cvd_frames_crc(const uint32_t* d_bits, int64_t rows, int32_t w, int32_t first, int32_t count,
+                   int32_t width, uint32_t poly, uint32_t init, uint32_t* d_value, void* stream);
+
 /* ---- error-exponent engine (alpha_exponent.py, Eq. 7) ---------------------
  * Joint counts of (metric state i, received word r) along received streams
  * (pitch = nseq) for steps t >= burn_in, on a dense (enumerated) model with
