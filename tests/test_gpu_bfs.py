@@ -2,10 +2,11 @@
 cvd_enumerate_device gives the reference's BFS -- the same states in the same
 discovery order and the same successor table -- as the reference's own goldens
 (tests/golden: m2, m3, rate 2/3 S = 1,807) and the host BFS (cvd_enumerate) on
-(23,35), S = 150,743; also with candidate chunks far smaller than a level and with
-the hash narrowed to a few bits, which forces the 64-bit-collision path (a hash
-shared by different states is never merged).  At m = 6 the search stops at its
-capacity and reports a lower bound with per-level sizes."""
+(23,35), S = 150,743; also with candidate chunks of the minimum size (1,024: two or
+three per level of r23_m4) and with the hash narrowed to a few bits, which forces the
+64-bit-collision path (a hash shared by different states is never merged).  At m = 6
+the search stops at its capacity and reports a lower bound with per-level sizes.
+Every kernel instance, chunk edge and stop in detail: test_gpu_bfs_edges.py."""
 import numpy as np
 import pytest
 
@@ -35,8 +36,11 @@ def test_gpu_bfs_equals_reference_goldens(pkg, golden, name):
 
 @pytest.mark.parametrize("chunk,bits", [("1024", "64"), ("64", "6"), ("100000", "3")])
 def test_gpu_bfs_small_chunks_and_forced_collisions(pkg, golden, monkeypatch, chunk, bits):
-    """Chunks smaller than a level (new states met again from a later chunk) and hashes
-    cut to `bits` bits (most states share a hash: each must still be kept apart)."""
+    """Chunks of the minimum size and hashes cut to `bits` bits (most states share a hash: each
+    must still be kept apart).  CVD_BFS_CHUNK below 1,024 is raised to 1,024, so "64" is a chunk
+    of 1,024 candidates like "1024": r23_m4's widest levels (up to 2,560 candidates) then take two
+    or three chunks (new states met again from a later chunk), m3_demo's levels (at most 352) one.
+    Levels of eight and more chunks and chunks that end at a level's end: test_gpu_bfs_edges.py."""
     monkeypatch.setenv("CVD_BFS_CHUNK", chunk)
     monkeypatch.setenv("CVD_BFS_HASH_BITS", bits)
     z, meta = golden
