@@ -25,7 +25,8 @@ from .decode import (PUNCTURE_PATTERNS, decode_capture, decode_capture_punctured
                      decode_frames_soft_punctured, decode_frames_tailbiting, decode_frames_tailbiting_soft,
                      decode_frames_tailbiting_soft_punctured, depuncture_soft, puncture_pattern, punctured_bits,
                      soft_from_bits, sync_punctured, sync_punctured_soft,
-                     CRC_SPECS, crc_spec, decode_frames_crc, decode_frames_list, frames_crc)
+                     CRC_SPECS, crc_spec, decode_frames_crc, decode_frames_list, frames_crc,
+                     decode_frames_tailbiting_crc, decode_frames_tailbiting_list)
 from .exponent import (  # noqa: F401
     TransitionTensor, learn_transition_tensor, chernoff_rhos, compute_error_exponent, spectral_radius,
     fit_error_exponent, EXPONENT_TAG,

@@ -226,6 +226,14 @@ EXPORTS = {
                                                       ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "cvd_viterbi_tailbiting_list_workspace_bytes": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                                                     ctypes.c_int64, ctypes.c_int32]),
+    "cvd_viterbi_decode_frames_tailbiting_list": (ctypes.c_int, [ctypes.POINTER(cvd_code), ctypes.c_void_p,
+                                                                 ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                                                                 ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32,
+                                                                 ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
+                                                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                                 ctypes.c_void_p, ctypes.c_void_p]),
     "cvd_frames_crc": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                       ctypes.c_int32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p,
                                       ctypes.c_void_p]),

@@ -56,27 +56,16 @@
 #include "../../include/cvd.h"
 #include "cvd_decode_common.h"
 #include "cvd_decode_lanes.h"
+#include "cvd_decode_list_common.h"
 #include "cvd_internal.h"
 
 namespace {
 
 using namespace cvd::vit;
 
-constexpr uint32_t kAbsent = 0x80000000u;          // above every key of a path
 constexpr uint32_t kNoHead = 0xffffffffu;          // end selection: a state without a remaining entry
-constexpr int kListWaves = 8192;                   // waves of the launch
-constexpr int64_t kListWorkBytes = (int64_t)1 << 30;
-// The tile of decisions in LDS.  16 KiB leaves ten waves per CU (160 KiB) at S <= 64 and six beside
-// the exchange buffer of S = 256, L = 8 (8 KiB); frames of 128 steps of 64 states fit it up to L = 4.
-constexpr int64_t kListLdsBytes = 16384;
-constexpr int64_t kListLdsMin = 1024, kListLdsMax = 49152;   // CVD_LIST_LDS_BYTES is clamped to these
 constexpr int kCrcThreads = 256;
 constexpr int kCrcBlocks = 4096;
-
-template <int LL> struct DecWord;
-template <> struct DecWord<2> { using type = uint8_t; };
-template <> struct DecWord<4> { using type = uint16_t; };
-template <> struct DecWord<8> { using type = uint32_t; };
 
 struct LsArgs {
   VArgs v;                   // cap, nu4, T, span, the code
@@ -101,26 +90,6 @@ __device__ __forceinline__ int64_t frame_offset(const LsArgs& la, int64_t f) {
   const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)((uint64_t)o >> 32));
   return (int64_t)(((uint64_t)hi << 32) | lo);
 }
-
-// the LL smallest of two ascending lists, ascending
-template <int LL>
-__device__ __forceinline__ void merge_lists(const uint32_t (&a)[LL], const uint32_t (&b)[LL], uint32_t (&o)[LL]) {
-#pragma unroll
-  for (int i = 0; i < LL; ++i) o[i] = min(a[i], b[LL - 1 - i]);
-#pragma unroll
-  for (int h = LL / 2; h >= 1; h >>= 1) {
-#pragma unroll
-    for (int i = 0; i < LL; ++i) {
-      if ((i & h) == 0) {
-        const uint32_t lo = min(o[i], o[i + h]), hi = max(o[i], o[i + h]);
-        o[i] = lo;
-        o[i + h] = hi;
-      }
-    }
-  }
-}
-
-extern __shared__ uint4 list_tile[];     // the tile of decisions: tile16 pieces
 
 template <int m, int n, int LL>
 __global__ __launch_bounds__(kWave) void viterbi_frames_list_kernel(LsArgs la) {
@@ -164,64 +133,19 @@ __global__ __launch_bounds__(kWave) void viterbi_frames_list_kernel(LsArgs la) {
     int tile = 0, tin = 0;
     for (int t0 = 0; t0 < T; t0 += kWave) {
       const int cnt = min(kWave, T - t0);
-      int vp = 0, ap = 0;                                // lane j < cnt: the values of step t0 + j, and their magnitudes' sum
-      if (lane < cnt) {
-        const int8_t* p = cap + o + (int64_t)n * (t0 + lane);
-#pragma unroll
-        for (int j = 0; j < n; ++j) {
-          const int x = max((int)p[j], -127);
-          ap += abs(x);
-          vp |= (x & 255) << (8 * j);
-        }
-      }
+      int vp, ap;                                        // lane j < cnt: the values of step t0 + j, and their magnitudes' sum
+      load_values<n>(cap + o, t0, cnt, lane, vp, ap);
       for (int jj = 0; jj < cnt; ++jj) {
         const int vs = __builtin_amdgcn_readlane(vp, jj);
         const int at = __builtin_amdgcn_readlane(ap, jj);
-        if constexpr (SPL > 1) {
-          __syncthreads();                               // the step before has read xk
+        uint32_t d[SPL];
+        list_step<m, n, LL>(ln, K, xk, vs, at, LL, d);
+        if (lane < S) {
 #pragma unroll
-          for (int i = 0; i < SPL; ++i) {
-#pragma unroll
-            for (int r = 0; r < LL; ++r) xk[r * S + ln.state(i)] = K[i][r];
-          }
-          __syncthreads();
-        }
-        uint32_t N[SPL][LL];
-#pragma unroll
-        for (int i = 0; i < SPL; ++i) {
-          const uint32_t add0 = (uint32_t)ln.cand0(i, vs, at) << 4;
-          const uint32_t add1 = ((uint32_t)ln.cand1(i, vs, at) << 4) | 8u;
-          uint32_t c0[LL], c1[LL];
-#pragma unroll
-          for (int r = 0; r < LL; ++r) {
-            uint32_t a0, a1;
-            if constexpr (SPL > 1) {
-              a0 = xk[r * S + ln.ps0[i]];
-              a1 = xk[r * S + ln.ps1[i]];
-            } else {
-              a0 = (uint32_t)__shfl((int)K[0][r], ln.ps0[0]);
-              a1 = (uint32_t)__shfl((int)K[0][r], ln.ps1[0]);
-            }
-            c0[r] = (a0 & ~15u) + add0 + (uint32_t)r;
-            c1[r] = (a1 & ~15u) + add1 + (uint32_t)r;
-          }
-          merge_lists<LL>(c0, c1, N[i]);
-        }
-#pragma unroll
-        for (int i = 0; i < SPL; ++i) {
-          uint32_t d = 0u;
-#pragma unroll
-          for (int r = 0; r < LL; ++r) {
-            K[i][r] = min(N[i][r], kAbsent);
-            d |= (N[i][r] & 15u) << (4 * r);
-          }
-          if (lane < S) dec[tin * S + ln.state(i)] = (E)d;
+          for (int i = 0; i < SPL; ++i) dec[tin * S + ln.state(i)] = (E)d[i];
         }
         if (++tin == tsteps && t0 + jj + 1 < T) {        // the tile is full and the frame goes on
-          __syncthreads();
-          uint4* g = slice + (int64_t)tile * la.tile16;
-          for (int k = lane; k < la.tile16; k += kWave) g[k] = list_tile[k];
-          __syncthreads();
+          tile_out(slice + (int64_t)tile * la.tile16, la.tile16, lane);
           tin = 0;
           ++tile;
         }
@@ -290,12 +214,7 @@ __global__ __launch_bounds__(kWave) void viterbi_frames_list_kernel(LsArgs la) {
     __syncthreads();                                     // the last tile is written
     for (int tl = ntiles - 1; tl >= 0; --tl) {
       const int tb = tl * tsteps, te = min(T, tb + tsteps);
-      if (tl != ntiles - 1) {
-        __syncthreads();                                 // the tile behind has been read
-        const uint4* g = slice + (int64_t)tl * la.tile16;
-        for (int k = lane; k < la.tile16; k += kWave) list_tile[k] = g[k];
-        __syncthreads();
-      }
+      if (tl != ntiles - 1) tile_in(slice + (int64_t)tl * la.tile16, la.tile16, lane);
       for (int t = te - 1; t >= tb; --t) {
         out |= (uint32_t)(s & 1) << (t & 31);
         const uint32_t d = dec[(t - tb) * S + s];
@@ -383,47 +302,6 @@ using LsKern = void (*)(LsArgs);
 constexpr const char* kWho = "viterbi_decode_frames_list";
 constexpr const char* kWhoCrc = "frames_crc";
 
-long long env_number(const char* name) {
-  const char* e = getenv(name);
-  return e ? atoll(e) : 0;
-}
-
-// kListWaves, or CVD_LIST_WAVES (a test's way to another launch shape)
-int64_t list_wave_cap() {
-  const long long v = env_number("CVD_LIST_WAVES");
-  return v > 0 ? std::min<int64_t>(v, kListWaves) : kListWaves;
-}
-
-// kListLdsBytes, or CVD_LIST_LDS_BYTES (a measurement's way to another tile)
-int64_t list_lds_bytes() {
-  const long long v = env_number("CVD_LIST_LDS_BYTES");
-  return v > 0 ? std::min(std::max<int64_t>(v, kListLdsMin), kListLdsMax) : kListLdsBytes;
-}
-
-int list_width(int L) { return L <= 2 ? 2 : L <= 4 ? 4 : 8; }
-
-// how a frame's decisions are tiled: tsteps steps of 2^m LL / 2 bytes each in LDS
-struct Tiling {
-  int64_t tsteps, ntiles, tile_bytes, slice_bytes;
-};
-
-Tiling tiling_of(int m, int64_t T, int L) {
-  const int64_t step = ((int64_t)1 << m) * list_width(L) / 2;      // <= 1024 <= kListLdsMin
-  Tiling t;
-  t.tsteps = std::min<int64_t>(T, list_lds_bytes() / step);
-  t.ntiles = (T + t.tsteps - 1) / t.tsteps;
-  t.tile_bytes = round16(t.tsteps * step);
-  t.slice_bytes = (t.ntiles - 1) * t.tile_bytes;
-  return t;
-}
-
-// waves of the launch: at most the frames, the cap, and what kListWorkBytes holds (monotone in F)
-int64_t list_waves(const Tiling& t, int64_t F) {
-  int64_t waves = std::min(F, list_wave_cap());
-  if (t.slice_bytes) waves = std::min(waves, std::max<int64_t>(1, kListWorkBytes / t.slice_bytes));
-  return waves;
-}
-
 }  // namespace
 
 extern "C" int64_t cvd_viterbi_list_workspace_bytes(int32_t n, int32_t m, int32_t T, int64_t F, int32_t L) {
@@ -480,12 +358,7 @@ extern "C" int cvd_viterbi_decode_frames_list(const cvd_code* code, const int8_t
   a.start = d_offsets ? 0 : start;
   a.T = T;
   a.span = span;
-  for (int j = 0; j < n; ++j) {
-    const uint8_t* t = code->taps + (size_t)j * (m + 1);
-    if (t[0] & 1) a.g0 |= 1u << j;
-    for (int d = 1; d <= m; ++d)
-      if (t[d] & 1) a.gs[j] |= 1u << (d - 1);
-  }
+  list_code_taps(code, a);
   a.bits = d_bits;
   la.offsets = d_offsets;
   la.stride = stride;

@@ -881,3 +881,110 @@ def decode_frames_crc(n, m, gen, soft, T, L, crc, first=0, count=None, expect=No
         res.update(value=value, choice=choice.to(torch.int32), crc_ok=ok, chosen_bits=res["bits"][rows, pick],
                    chosen_distance=res["distance"][rows, pick], ok=int(ok.sum()), rescued=int((choice > 0).sum()))
     return res
+
+
+# ─────────────────── list decoding of tail-biting frames ────────────────────
+
+def decode_frames_tailbiting_list(n, m, gen, soft, T, L, F=None, start=0, stride=None, offsets=None, max_laps=None,
+                                  device=None):
+    """cvd_viterbi_decode_frames_tailbiting_list: decode_frames_tailbiting_soft returning up to L
+    paths of every frame, 1 <= L <= 8, 1 <= T <= 8192: path 0 is decode_frames_tailbiting_soft's,
+    paths 1.. are the cheapest tail-biting entries (s_0 = s_T) of the last lap's end lists, in
+    ascending order of their distance (one of them may be cheaper than a path 0 of status 2 or 3).
+    The frames of the soft capture `soft` (int8) are placed as decode_frames places them; start,
+    stride and offsets count values; max_laps as in decode_frames_tailbiting (1..8; None: 4).
+    The result for L is not the first L paths of the result for a larger L.
+    Returns a dict: bits (device uint8 [F, L, 4w], w = ceil(T/32): row (f, l) is path l of frame f,
+    LSB-packed, zero where the path is absent), distance, start_states, end_states (device int32
+    [F, L]; -1 where absent), frames (device int32 [F, 4]) and the views of its columns paths (how
+    many were found), status (0, 2, 3 as decode_frames_tailbiting; 1 skipped), laps and candidates
+    (the tail-biting entries of the last lap, |C|); total_distance (of the paths 0), decoded,
+    skipped, total_paths, words (w), fallback (frames of status 2), open (status 3), total_laps, T,
+    F, L.  Python and C only: the command line does not reach it."""
+    dev = device if isinstance(device, torch.device) else _require_gpu(device)
+    n, m, T, L = int(n), int(m), int(T), int(L)
+    code = as_code(gen, m, 1, n)
+    cap, nvals = _soft_buffer(soft, dev)
+    if not 1 <= T <= LIST_MAX_T:
+        raise ValueError(f"T = {T}: a frame of the list decoder has 1..{LIST_MAX_T} steps")
+    if not 1 <= L <= LIST_MAX_L:
+        raise ValueError(f"L = {L}: the list holds 1..{LIST_MAX_L} paths")
+    laps = 0 if max_laps is None else int(max_laps)
+    if max_laps is not None and not 1 <= laps <= TAILBITING_MAX_LAPS:
+        raise ValueError(f"max_laps = {max_laps}: 1..{TAILBITING_MAX_LAPS} laps, or None for {TAILBITING_LAPS}")
+    w = (T + 31) // 32
+    off, F, start, stride = _frame_placement(nvals, n * T, L * w, F, start, stride, offsets, dev)
+    lib = _lib.lib()
+    call = lib.cvd_viterbi_decode_frames_tailbiting_list
+    wbytes = int(lib.cvd_viterbi_tailbiting_list_workspace_bytes(n, m, T, F, L))
+    if wbytes < 0:
+        # the decoder itself names an unsupported code shape
+        _lib.check(call(code.c, None, 0, 0, 1, None, 0, T, laps, L, None, None, None, None, None, None))
+        _lib.check(wbytes)
+    with torch.cuda.device(dev):
+        bits = torch.empty((F, L, 4 * w), dtype=torch.uint8, device=dev)
+        paths = torch.empty((F, L, 3), dtype=torch.int32, device=dev)
+        frames = torch.empty((F, 4), dtype=torch.int32, device=dev)
+        s = [0, 0, 0, 0, w, 0, 0, 0]
+        if F:
+            free = torch.cuda.mem_get_info(dev)[0]
+            if wbytes > free:
+                raise MemoryError(f"decode_frames_tailbiting_list: the workspace of {F} frames of T = {T} steps (m = {m}, "
+                                  f"L = {L}) is {wbytes} bytes, {free} bytes of device memory are free: decode the "
+                                  f"frames in pieces")
+            stats = torch.zeros(8, dtype=torch.int64, device=dev)
+            work = torch.empty(wbytes, dtype=torch.uint8, device=dev) if wbytes else None
+            _lib.check(call(code.c, ctypes.c_void_p(cap.data_ptr()), nvals, start, stride,
+                            ctypes.c_void_p(off.data_ptr()) if off is not None else None, F, T, laps, L,
+                            ctypes.c_void_p(bits.data_ptr()), ctypes.c_void_p(paths.data_ptr()),
+                            ctypes.c_void_p(frames.data_ptr()), ctypes.c_void_p(stats.data_ptr()),
+                            ctypes.c_void_p(work.data_ptr()) if work is not None else None, _stream_ptr()))
+            s = stats.cpu().tolist()     # synchronises: cap, off and work may be freed on return
+    return {"bits": bits, "distance": paths[:, :, 0], "start_states": paths[:, :, 1], "end_states": paths[:, :, 2],
+            "frames": frames, "paths": frames[:, 0], "status": frames[:, 1], "laps": frames[:, 2],
+            "candidates": frames[:, 3], "total_distance": int(s[0]), "decoded": int(s[1]), "skipped": int(s[2]),
+            "total_paths": int(s[3]), "words": int(s[4]), "fallback": int(s[5]), "open": int(s[6]),
+            "total_laps": int(s[7]), "T": T, "F": F, "L": L}
+
+
+def decode_frames_tailbiting_crc(n, m, gen, soft, T, L, crc, first=0, count=None, expect=None, F=None, start=0,
+                                 stride=None, offsets=None, max_laps=None, device=None):
+    """decode_frames_tailbiting_list and the CRC `crc` (anything crc_spec takes) over all F L rows
+    on the device: of every frame the first path of the list that passes the check (LTE PBCH and
+    PDCCH, 802.16 FCH, EDGE control blocks: short tail-biting frames that end in a CRC).  The CRC
+    runs over `count` bits from bit `first` (count=None: T - first - width, a frame of data || CRC)
+    and a path passes when its value equals `expect` (None: the spec's).  Where the CRC is masked
+    with an identity (the RNTI of an LTE DCI) and the identity is known, pass it as `expect`; where
+    it is not, leave expect=None and read the identity out of `value`: value[f, l] is register ^
+    field of path l, which is the mask that the sender applied if the path is the sent one (choice,
+    crc_ok and rescued then only mark the paths whose mask is the spec's own `expect`).
+    Returns decode_frames_tailbiting_list's dict and: value (device int64 [F, L]), choice (device
+    int32 [F]: the lowest present l whose value equals expect, -1 if none), crc_ok (device bool
+    [F]), chosen_bits (device uint8 [F, 4w]: the chosen row, path 0 where none passes),
+    chosen_distance (device int32 [F]), and the totals ok (frames with crc_ok) and rescued (frames
+    with choice > 0)."""
+    dev = device if isinstance(device, torch.device) else _require_gpu(device)
+    n, m, T, L = int(n), int(m), int(T), int(L)
+    width, poly, init, exp0 = crc_spec(crc)
+    expect = exp0 if expect is None else int(expect)
+    if expect < 0 or expect >> width:
+        raise ValueError(f"expect = {expect}: a value below 2^{width}")
+    first = int(first)
+    count = T - width - first if count is None else int(count)
+    if first < 0 or count < 0 or first + count + width > T:
+        raise ValueError(f"first = {first}, count = {count}: the data and the {width} CRC bits must lie inside the "
+                         f"{T} bits of a frame")
+    res = decode_frames_tailbiting_list(n, m, gen, soft, T, L, F=F, start=start, stride=stride, offsets=offsets,
+                                        max_laps=max_laps, device=dev)
+    F = res["F"]
+    with torch.cuda.device(dev):
+        value = frames_crc(res["bits"], first, count, (width, poly, init, expect), device=dev)
+        present = torch.arange(L, device=dev)[None, :] < res["paths"][:, None]
+        hit = (value == expect) & present
+        ok = hit.any(dim=1)
+        choice = torch.where(ok, hit.to(torch.int32).argmax(dim=1), torch.full_like(res["paths"], -1, dtype=torch.int64))
+        pick = choice.clamp(min=0)
+        rows = torch.arange(F, device=dev)
+        res.update(value=value, choice=choice.to(torch.int32), crc_ok=ok, chosen_bits=res["bits"][rows, pick],
+                   chosen_distance=res["distance"][rows, pick], ok=int(ok.sum()), rescued=int((choice > 0).sum()))
+    return res

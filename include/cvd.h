@@ -945,6 +945,82 @@ int cvd_viterbi_decode_frames_list(const cvd_code* code, const int8_t* d_soft, i
                                    int32_t start_state, int32_t end_state, int32_t L,
                                    uint32_t* d_bits, int32_t* d_paths, int32_t* d_frames, int64_t* d_stats,
                                    void* d_work, void* stream);
+
+/* ---- list decoding of tail-biting soft frames (nothing in the reference) ----
+ * The tail-biting frames that the calls above were built for are short frames that end in a CRC:
+ * LTE PBCH and PDCCH / DCI (CRC-16, masked with the RNTI on a DCI), 802.16 FCH, EDGE control
+ * blocks.  cvd_viterbi_decode_frames_tailbiting_soft returns one path per frame, and
+ * cvd_viterbi_decode_frames_list needs boundary states that such a frame does not have.  This call
+ * returns up to L tail-biting paths of every frame, for cvd_frames_crc to choose from.
+ * Inherited unchanged from cvd_viterbi_decode_frames_tailbiting_soft: the code shapes, the int8
+ * capture, cost(out, t), the placement of the frames and skipped frames, states, branches and the
+ * tie rule, max_laps = I (0: CVD_VITERBI_TAILBITING_LAPS, at most CVD_VITERBI_TAILBITING_MAX_LAPS),
+ * and that T < m is allowed.  From cvd_viterbi_decode_frames_list: 1 <= L <= CVD_VITERBI_LIST_MAX_L,
+ * 1 <= T <= CVD_VITERBI_LIST_MAX_T, F*L*w < 2^31 with w = ceil(T/32), and the layout of d_bits
+ * (row f*L + l holds path l of frame f; the row of an absent path is zero).
+ * The decoder of one frame (a sequential decoder written from this text reproduces every output bit
+ * for bit).  E^0(s) = 0 for every s.  Laps l = 1, 2, ...:
+ *   forward    T steps of the list recursion of cvd_viterbi_decode_frames_list from
+ *              A^l_0(s) = [E^{l-1}(s)], one entry in every state: the candidates in ascending order
+ *              of (c, b, r), lists of at most L entries, dec^l_t(s')[rank] = (b, r); every lap reads
+ *              the same T received words.
+ *   normalise  D^l_T(s) = A^l_T(s)[0]; E^l(s) = D^l_T(s) - min_s D^l_T(s); e* = the lowest-index
+ *              state of minimal D^l_T.
+ *   trace      for every present entry (e, r) of every end state, a^l(e, r) = the state at step 0
+ *              that the list call's traceback reaches from (s_T, r_T) = (e, r) through dec^l.
+ *   stop       the rule of cvd_viterbi_decode_frames_tailbiting_soft on rank 0: with
+ *              B^l = {e : a^l(e, 0) = e}, lap l is the last if e* is in B^l (status 0), or if l = I, or
+ *              if l >= 2 and E^l = E^{l-1} as vectors; in the last two cases the status is 2 if B^l
+ *              is not empty and 3 if it is.  Not the last lap: go on to lap l + 1.
+ *   On the last lap: C = {(e, r) present : a^l(e, r) = e}, the tail-biting entries, and
+ *   c(e, r) = A^l_T(e)[r] - E^{l-1}(a^l(e, r)), the cost of the entry's path over the frame's own T
+ *   steps.  Path 0 is the path that cvd_viterbi_decode_frames_tailbiting_soft returns: the entry
+ *   (e0, 0) with e0 = e* for status 0 and 3, and the e in B^l of minimal c(e, 0), lowest index on
+ *   ties, for status 2.  Paths 1, 2, ... are the members of C other than (e0, 0) in ascending order
+ *   of the triple (c, e, r), the first L - 1 of them: P = 1 + min(L - 1, |C \ {(e0, 0)}|) paths.
+ *   Every path is traced as in the list call (u_t, s_0 as traced, s_T = e) and reported with its c.
+ * Consequences (checked on a sequential decoder of this text):
+ *   L = 1 is cvd_viterbi_decode_frames_tailbiting_soft in bits, [0], [1], [2], status and laps, and
+ *   for every L path 0, the status and the laps are (on rank 0 the order (c, b, r) is `val < best`);
+ *   paths l >= 1 are tail-biting (s_0 = s_T), pairwise distinct as rows, and distinct from a
+ *   tail-biting path 0 (a path 0 of status 3 is not tail-biting, and a path l >= 1 may have its row);
+ *   c is non-decreasing from l = 1 on;
+ *   a path l >= 1 may be cheaper than path 0, of status 0 or 2 too (path 0 is chosen among the
+ *   ranks 0 by D^l_T, which holds E^{l-1} of the start state; about 2% of frames at a noise of 1.5
+ *   amplitudes);
+ *   the result for L is NOT a prefix of the result for a larger L: an entry of rank >= L can be
+ *   tail-biting where the lower ranks of its state are not, so lists of more entries find other
+ *   members of C.  An implementation whose lists hold more than L entries must make ranks >= L
+ *   absent at every step.
+ * d_paths: int32[F][L][3], 4-byte aligned: {c, s_0, s_T}; an absent path is {-1, -1, -1}.
+ * d_frames: int32[F][4], 4-byte aligned: {P, status (0, 2 or 3 as above; 1 skipped), laps run, |C|}.
+ * A skipped frame has zero rows, absent paths and {0, 1, 0, 0}, and nothing is read for it.
+ * d_stats: int64[8], written (not accumulated), 8-byte aligned:
+ *   [0] sum of the path-0 c  [1] frames decoded  [2] frames skipped  [3] sum of P  [4] w
+ *   [5] frames of status 2  [6] frames of status 3  [7] sum of laps
+ * All sums are integer sums, so the result does not depend on the launch shape.
+ * CVD_E_INVALID (CVD_E_UNSUPPORTED for the code shape), before the device is touched,
+ * cvd_last_error() naming viterbi_decode_frames_tailbiting_list, for every case that
+ * cvd_viterbi_decode_frames_tailbiting_soft and cvd_viterbi_decode_frames_list list (but those about
+ * the boundary states): nvals < 0; F < 0; max_laps outside 0..8; L outside 1..8; in stride mode
+ * start < 0 or stride < 1; and when F > 0: T outside 1..8192; F*L*w >= 2^31 words; in stride mode
+ * start + (F-1)*stride + n*T > nvals or an int64 overflow on the way; null or misaligned pointers
+ * (d_soft, d_work 16-byte, d_stats, d_offsets 8-byte, d_bits, d_paths, d_frames 4-byte aligned).
+ * F == 0: CVD_OK without a launch (nothing is written).
+ * d_work: cvd_viterbi_tailbiting_list_workspace_bytes(n, m, T, F, L) bytes, 16-byte aligned: the
+ * tiling of cvd_viterbi_list_workspace_bytes, to the byte (a tile of decisions in LDS, the other
+ * tiles of a frame in a slice per wave of the launch; 0, and a null d_work allowed, when a frame's
+ * decisions fit the tile).  CVD_LIST_WAVES and CVD_LIST_LDS_BYTES apply, read at both calls.  0 at
+ * F == 0; < 0 with the error set for n, m outside the shapes, L outside 1..8, T outside 1..8192 or
+ * F < 0.  Asynchronous on `stream`: one launch.  Kernels: csrc/cvd_decode_tblist.hip.  The rows are
+ * in the layout that cvd_frames_crc reads. */
+int64_t cvd_viterbi_tailbiting_list_workspace_bytes(int32_t n, int32_t m, int32_t T, int64_t F, int32_t L);
+int cvd_viterbi_decode_frames_tailbiting_list(const cvd_code* code, const int8_t* d_soft, int64_t nvals,
+                                              int64_t start, int64_t stride, const int64_t* d_offsets, int64_t F,
+                                              int32_t T, int32_t max_laps, int32_t L,
+                                              uint32_t* d_bits, int32_t* d_paths, int32_t* d_frames, int64_t* d_stats,
+                                              void* d_work, void* stream);
+
 /* A CRC over rows of bits in any layout that the decoders write (cvd_viterbi_decode_frames*, the
  * tail-biting calls, the list): `rows` rows of w words, bit t of a row = bit (t & 31) of word
  * t >> 5, called u_t.  One 32-bit value per row.  With mask = 2^width - 1:
