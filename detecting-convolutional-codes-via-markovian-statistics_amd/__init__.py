@@ -15,8 +15,9 @@ from .detector import (  # noqa: F401
 from .parity import (  # noqa: F401
     parse_poly_token, build_parity_system, nullspace_mod2, parity_vector_to_equation, parity_vectors,
     template_of, default_template, parity_detect, parity_satisfaction_fraction, parity_detector,
-    parity_experiment,
+    parity_experiment, encode_convolutional,
 )
+from .encode import encode_capture, encode_frames, pack_info, unpack_info  # noqa: F401
 from .blind import (  # noqa: F401
     template_mask, mask_template, mask_extent, parity_sweep, find_parity_checks, identify_code, default_z_min,
 )

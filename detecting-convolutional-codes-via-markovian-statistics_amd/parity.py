@@ -5,6 +5,7 @@ Reference (So-bonkers/Detecting-Convolutional-Codes-Via-Markovian-Statistics):
   parity_eqn_check.nullspace_mod2            parity_eqn_check.py:93-141
   parity_eqn_check.build_parity_system       parity_eqn_check.py:148-181
   parity_eqn_check.parity_vector_to_equation parity_eqn_check.py:188-201
+  comp_parity.encode_convolutional           comp_parity.py:65-83
   comp_parity.parity_satisfaction_fraction   comp_parity.py:90-117
   comp_parity.parity_detector                comp_parity.py:120-128
   comp_parity.__main__ (template choice, MC) comp_parity.py:135-181
@@ -139,6 +140,25 @@ def parity_detect(r, n, N, nseq, n_h1, template, gamma, sat=None, counts=None, d
         float(gamma), ctypes.c_void_p(sat.data_ptr() if sat is not None else 0),
         ctypes.c_void_p(counts.data_ptr()), _stream_ptr(stream)))
     return counts
+
+
+def encode_convolutional(u_bits, generators, m, device=None):
+    """The noiseless codeword of u_bits (comp_parity.py:65-83): n lists of len(u_bits) + m bits,
+    outputs[j][t] = XOR of the tapped u_{t-shift}, zeros outside the input.  One terminated
+    cvd_encode_frames call on the GPU (encode.encode_frames); ValueError outside k = 1,
+    n in 2..3, m <= 16 and tap lists of at most m + 1 entries."""
+    from .encode import MAX_M, encode_frames, pack_info
+    n, m = len(generators), int(m)
+    if n not in (2, 3) or any(len(g) != 1 for g in generators) or not 1 <= m <= MAX_M:
+        raise ValueError("encode_convolutional on the GPU needs k = 1, n in 2..3 and 1 <= m <= 16")
+    if any(len(g[0]) > m + 1 for g in generators):
+        raise ValueError(f"a tap list is longer than m + 1 = {m + 1}")
+    u = [int(b) for b in u_bits]
+    T = len(u) + m
+    res = encode_frames(n, m, generators, pack_info(np.array(u + [0] * m, np.uint8)), T, 1, "terminated", 0,
+                        device=device)
+    v = res["capture"].cpu().numpy().reshape(T, n)
+    return [v[:, j].tolist() for j in range(n)]
 
 
 def parity_satisfaction_fraction(y, template, device=None):

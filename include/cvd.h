@@ -1042,6 +1042,63 @@ int cvd_viterbi_decode_frames_tailbiting_list(const cvd_code* code, const int8_t
 int cvd_frames_crc(const uint32_t* d_bits, int64_t rows, int32_t w, int32_t first, int32_t count,
                    int32_t width, uint32_t poly, uint32_t init, uint32_t* d_value, void* stream);
 
+/* ---- encoder: information bits -> a capture (comp_parity.py encode_convolutional, batched) ----
+ * The inverse of the frames decoders: F rows of information bits become one capture that every
+ * cvd_viterbi_decode* call accepts as it stands, so that decode(encode(u)) == u and
+ * encode(decode(y)) ^ y (where the channel errors are) are one call each.
+ * Code shapes: k = 1, n in {2, 3}, 1 <= m <= 16 (an encoder has no 2^m anywhere; the blind
+ * search finds codes past the decoders' m = 8); anything else CVD_E_UNSUPPORTED.  States,
+ * branches and tap order are cvd_viterbi_decode's.
+ * Input: d_info, F rows of `pitch` words, pitch >= w = ceil(T/32); bit t of row f = bit (t & 31)
+ * of word f*pitch + (t >> 5) is u_t: the d_bits layout of every frames decoder (with
+ * pitch = L*w and the pointer moved by i*w words it reads path i of a list result).  Bits of a
+ * row at or past T are ignored and need not be zero.  4-byte aligned.
+ * Coded bits of a frame: output j of step t, 0 <= t < T, is
+ *   c_{t,j} = XOR_{d=0..m} taps[j][0][d] * u_{t-d},
+ * where, by mode: */
+#define CVD_ENCODE_OPEN       0  /* u_{-d} = bit d-1 of start_state, d = 1..m */
+#define CVD_ENCODE_TERMINATED 1  /* as OPEN, and u_t is taken as 0 for t >= T - m whatever the row holds */
+#define CVD_ENCODE_TAILBITING 2  /* u_{-d} = u_{(T-d) mod T}; start_state is ignored */
+#define CVD_CAPTURE_SOFT      3  /* output only: one int8 per channel bit, +A for a 1, -A for a 0 */
+/* TERMINATED needs T >= m: a decoder's row, tail included, re-encodes as it is, and a row of
+ * T - m data bits needs no zeroing.  TAILBITING allows T < m, as the tail-biting decoders do;
+ * the encoder ends in the state it started in.
+ * Puncturing: keep == NULL: none; frame position n*t + j holds c_{t,j} and span = n*T.
+ * Otherwise keep / period / pos(t) are exactly cvd_viterbi_decode_punctured's, with o_f in the
+ * place of start (the pattern restarts at column 0 in every frame): only the outputs j with bit
+ * j of keep[t mod period] are emitted, j ascending, at pos(t), pos(t)+1, ...; span = pos(T) - o_f.
+ * Output: `nout` positions (bits; bytes for CVD_CAPTURE_BYTES / _SOFT) in format
+ * CVD_CAPTURE_LSB / _MSB / _BYTES, read back exactly as the decoders read them, or
+ * CVD_CAPTURE_SOFT (amplitude = A, 1 <= A <= 127; amplitude must be 0 in the other formats).
+ * d_out is 16-byte aligned and holds the byte length of nout (ceil(nout/8), or nout) rounded up
+ * to 16.  The call writes all of it: every position that no frame covers, and the padding, is 0
+ * (bit 0; an erasure in SOFT).  Nothing at or past the rounded length is touched.
+ * Placement: d_offsets == NULL (stride mode): o_f = start + f*stride, stride >= span.
+ * Otherwise o_f = d_offsets[f] (a device array of F int64, 8-byte aligned; BYTES and SOFT only;
+ * start and stride are ignored): a frame with o_f < 0 or o_f + span > nout is skipped and
+ * nothing is written for it; where frames overlap, a shared position holds the value of one of
+ * the frames that cover it, unspecified which.
+ * d_stats: NULL, or int64[2], 8-byte aligned, written (not accumulated): [0] frames written,
+ * [1] frames skipped.
+ * The result is exact and does not depend on the launch shape (the environment variable
+ * CVD_ENCODE_BLOCKS, read at the call, caps the blocks of a launch).  Asynchronous on `stream`.
+ * CVD_E_INVALID, before the device is touched, cvd_last_error() naming encode_frames, for: a
+ * null code; an unknown mode or format; an amplitude outside 1..127 in SOFT or nonzero
+ * otherwise; start_state outside [0, 2^m) in OPEN or TERMINATED; F < 0 or nout < 0; d_offsets
+ * in a packed format; a bad pattern (as cvd_viterbi_decode_punctured reports it); in stride mode
+ * start < 0 or stride < 1; and when F > 0: T outside 1..2^31 - 1; TERMINATED with T < m;
+ * pitch < w; in stride mode stride < span (frames would overlap) or
+ * start + (F-1)*stride + span > nout; an int64 overflow on the way to the span, F*pitch or the
+ * last frame's end; a null or misaligned d_info (4-byte) or d_out (16-byte); a misaligned
+ * d_offsets or d_stats (8-byte).  F == 0: CVD_OK without a launch (nothing is written).
+ * Kernels: csrc/cvd_encode.hip. */
+int cvd_encode_frames(const cvd_code* code, const uint8_t* keep, int32_t period,
+                      const uint32_t* d_info, int64_t pitch, int64_t F, int64_t T,
+                      int32_t mode, int32_t start_state,
+                      int32_t format, int32_t amplitude,
+                      void* d_out, int64_t nout, int64_t start, int64_t stride, const int64_t* d_offsets,
+                      int64_t* d_stats, void* stream);
+
 /* ---- error-exponent engine (alpha_exponent.py, Eq. 7) ---------------------
  * Joint counts of (metric state i, received word r) along received streams
  * (pitch = nseq) for steps t >= burn_in, on a dense (enumerated) model with
